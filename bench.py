@@ -1,6 +1,15 @@
 """bench.py -- LangSplat train step on MI355X: rasterizer fwd+bwd blends/s and train-step ms.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C4|C5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C3|C2|C4|C5] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline]]
+
+A plain run sets up, runs W eager warm-up steps, times K steps of the form `value` comes from (the
+pipelined HIP-graph step, after its own untimed replays), writes that form's last outputs with
+--dump-outputs (DIR/loss.npy: the loss the last timed step returned, fp32; the inputs are seeded: the
+same from run to run) and prints one JSON line.  --full adds every other figure described below (the
+other step forms, the all-gradients step, the forward alone, the stage breakdown, reps and the synced
+form, the RGB step, the roofline, the CPU baseline); `value` is then the fastest of the full-step
+forms it timed.
 
 BASELINE.json metric: "train-step ms & Gaussian-pixel blends/sec (fwd+bwd) @1M Gaussians 1080p,
 1/2/4/8 GPU".  One step mirrors train.py:76-138 in LangSplat's language-feature mode
@@ -375,7 +384,15 @@ def main():
     ap.add_argument("--config", default=None)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also time every other step form and side figure (all-gradients step, forward only, "
+                         "eager and pipelined forms, stage breakdown, reps, synced form, RGB step, roofline, "
+                         "CPU baseline); `value` is then the fastest full-step form")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step of the `value` form computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if launch.should_launch(args.gpus):
         # a plain `python bench.py --gpus N`: start the N ranks here (before anything touches the GPU)
         sys.exit(launch.launch([os.path.abspath(__file__)] + sys.argv[1:], args.gpus))
@@ -459,64 +476,93 @@ def main():
     gc.collect()
     gc.disable()
 
-    # eager passes first (the captured graph then owns the parameters' .grad tensors):
-    # (2) the same step with every geometry gradient computed although no parameter needs one (what
-    # the reference extension does; LSR_ALL_GRADS=1): reported beside, never as `value`
-    _native.FORCE_GEOMETRY_GRADS = True
-    for _ in range(2):
-        step()
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    elapsed_all = time.perf_counter() - t1
-    _native.FORCE_GEOMETRY_GRADS = os.environ.get("LSR_ALL_GRADS", "0") == "1"
-    # (2b) the inference form (render.py:24-55: render() under torch.no_grad(), LSR_FWD_NO_BACKWARD):
-    # the forward alone, reported beside, never as `value`
-    with torch.no_grad():
+    # The full-step forms: eager (3), pipelined (5), pipelined_graph (6).  --full times every one of them
+    # and `value` is the fastest; a plain run times one, the form `value` comes from at the benched
+    # configs: the pipelined graph (the pipelined or the eager form where LSR_PIPELINE / LSR_GRAPH /
+    # LANGSPLAT_AMD_FUSED switch it off).  N > 1: the eager form as well, which stays `value` if the
+    # capture with the collective inside fails (below).
+    pipelined = fused and os.environ.get("LSR_PIPELINE", "1") != "0"
+    graphed = pipelined and os.environ.get("LSR_GRAPH", "1") != "0"
+    headline = "pipelined_graph" if graphed else "pipelined" if pipelined else "eager"
+    timed = {"eager", "pipelined", "pipelined_graph"} if args.full else {headline} | ({"eager"} if world > 1 else set())
+    # --dump-outputs: what the last timed step of each form handed its caller (rank 0's), cloned outside
+    # the timed regions: the step's loss.  The parameter the step updates in place and its gradient are
+    # not written: with Adam's eps 1e-15 an entry whose gradient is float-atomic noise (an occluded
+    # Gaussian's, ~1e-12) moves by +-lr per step with that noise's sign, so after the run's steps ~9 % of
+    # their entries differ between two runs of one build (by up to 0.9 at C3 after 2000 steps), while the
+    # loss over all pixels, which every kernel of every step so far feeds, repeats to ~1e-7 (measured;
+    # tests/test_gpu_captured_forms.py compares the forms' states above that noise floor)
+    snaps = {}
+
+    def snapshot(form, loss):
+        if args.dump_outputs and rank == 0:
+            snaps[form] = {"loss": loss.detach().clone()}
+
+    elapsed_all = elapsed_fwd = None
+    if args.full:
+        # eager passes first (the captured graph then owns the parameters' .grad tensors):
+        # (2) the same step with every geometry gradient computed although no parameter needs one (what
+        # the reference extension does; LSR_ALL_GRADS=1): reported beside, never as `value`
+        _native.FORCE_GEOMETRY_GRADS = True
         for _ in range(2):
-            render(cam, model, Pipe, bg, Opt)
+            step()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         for _ in range(args.steps):
-            render(cam, model, Pipe, bg, Opt)
+            step()
         torch.cuda.synchronize()
-        elapsed_fwd = time.perf_counter() - t1
+        elapsed_all = time.perf_counter() - t1
+        _native.FORCE_GEOMETRY_GRADS = os.environ.get("LSR_ALL_GRADS", "0") == "1"
+        # (2b) the inference form (render.py:24-55: render() under torch.no_grad(), LSR_FWD_NO_BACKWARD):
+        # the forward alone, reported beside, never as `value`
+        with torch.no_grad():
+            for _ in range(2):
+                render(cam, model, Pipe, bg, Opt)
+            if world > 1:
+                dist.barrier()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                render(cam, model, Pipe, bg, Opt)
+            torch.cuda.synchronize()
+            elapsed_fwd = time.perf_counter() - t1
     # (3) the eager step itself (the host enqueues every launch, one wait per forward)
-    if world > 1:
-        dist.barrier()
-    torch.cuda.synchronize()
-    te = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    elapsed_eager = time.perf_counter() - te
-    # (3b) the dominant kernel's average launch time, HIP events around it on its stream (every step)
-    _native.profile_enable(True, stages=[DOMINANT_STAGE], every=1)
-    for _ in range(min(args.steps, 20)):
-        step()
-    torch.cuda.synchronize()
-    _native.profile_enable(False)
-    dom = _native.profile_report().get(DOMINANT_STAGE, {"avg_ms": float("nan")})
-    # (4) stage breakdown: every stage profiled
-    prof_steps = min(args.steps, 10)
-    _native.profile_enable(True)
-    for _ in range(prof_steps):
-        step()
-    torch.cuda.synchronize()
-    _native.profile_enable(False)
-    prof = _native.profile_report()
+    elapsed_eager = float("inf")
+    if "eager" in timed:
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize()
+        te = time.perf_counter()
+        for _ in range(args.steps):
+            loss = step()
+        torch.cuda.synchronize()
+        elapsed_eager = time.perf_counter() - te
+        snapshot("eager", loss)
+    dom = prof = prof_steps = None
+    if args.full:
+        # (3b) the dominant kernel's average launch time, HIP events around it on its stream (every step)
+        _native.profile_enable(True, stages=[DOMINANT_STAGE], every=1)
+        for _ in range(min(args.steps, 20)):
+            step()
+        torch.cuda.synchronize()
+        _native.profile_enable(False)
+        dom = _native.profile_report().get(DOMINANT_STAGE, {"avg_ms": float("nan")})
+        # (4) stage breakdown: every stage profiled
+        prof_steps = min(args.steps, 10)
+        _native.profile_enable(True)
+        for _ in range(prof_steps):
+            step()
+        torch.cuda.synchronize()
+        _native.profile_enable(False)
+        prof = _native.profile_report()
 
     # (5) the pipelined form (langsplat_amd.pipeline.ViewPipeline): consecutive steps on two alternating
     # streams, each forward deferring the language feature until the previous update has landed, so the
     # next view's geometry stages run beside this view's backward, [all-reduce] and Adam.  Eager launches.
     elapsed_pipe = float("inf")
-    if fused and os.environ.get("LSR_PIPELINE", "1") != "0":
+    if pipelined and "pipelined" in timed:
         pipe = ViewPipeline(optim, bucket=bucket)
         optim.zero_grad(set_to_none=True)
 
@@ -534,12 +580,13 @@ def main():
         torch.cuda.synchronize()
         tp = time.perf_counter()
         for _ in range(args.steps):
-            run_pipe()
+            loss = run_pipe()
         pipe.synchronize()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         elapsed_pipe = time.perf_counter() - tp
+        snapshot("pipelined", loss)
         del pipe
 
     # The serial HIP-graph form (langsplat_amd.graph.GraphedStep: the whole step as one graph per
@@ -547,7 +594,6 @@ def main():
     # kernel tracer, profiles/r05_graph_vs_eager.txt), and each replay adds a graph boundary (idle
     # queue between consecutive graph launches) that the eager launches do not pay
     # (driver, round 4: 0.521 vs 0.497 ms).  The pipelined graph below is the captured form.
-    graphed = fused and os.environ.get("LSR_GRAPH", "1") != "0"
     # (6) the pipelined order as HIP graphs on two streams (langsplat_amd.pipeline.PipelinedGraphStep):
     # each replay is one full step -- this view's compositing, loss, backward and Adam on one stream, the
     # next view's geometry stages (the forward's first half) on the other -- with no host work inside
@@ -586,14 +632,18 @@ def main():
         # (replay(wait=False), no per-step join with the caller's stream, measured slower: 0.477 vs
         # 0.420 ms per step, tools/pg_host.py --nowait)
         for _ in range(args.steps):
-            pg.replay()
+            loss = pg.replay()
         pg.synchronize()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         elapsed_pg = time.perf_counter() - tq
+        snapshot("pipelined_graph", loss)
         if not pg.check():
             raise RuntimeError("a pipelined view exceeded its capacities during the timed steps")
+        if not args.full:
+            del pg
+            return elapsed_pg, float("inf"), rot, reps
         # the spread of this form over further reps of the same K steps (not `value`: the run-to-run
         # levels of DESIGN.md §5b), and train.py:108's loss.item() after every step
         # (ms_per_step_with_sync: a device-to-host sync per step, no run-ahead)
@@ -623,7 +673,7 @@ def main():
         return elapsed_pg, elapsed_sync, rot, reps
 
     pg_error = None
-    if graphed and os.environ.get("LSR_PIPELINE", "1") != "0":
+    if graphed:  # every run times this form where it is on
         if world == 1:
             elapsed_pg, elapsed_sync, pg_rot, pg_reps = run_pipelined_graph()
         else:
@@ -641,7 +691,7 @@ def main():
     # the RGB stage's step on the same scene and view (all six groups trainable, L1 + SSIM, densification
     # statistics): reported beside, never as `value`
     rgb_ms = None
-    if os.environ.get("LSR_BENCH_RGB", "1") != "0":
+    if args.full and os.environ.get("LSR_BENCH_RGB", "1") != "0":
         gtimg = torch.rand((3, H, W), generator=torch.Generator().manual_seed(200 + view)).to(dev)
         rgb = RGBStep(make_gaussians(P, seed=0, sh_degree=c["sh_degree"]).to(dev), cam, gtimg, bucket_world=world)
         for _ in range(3):
@@ -682,6 +732,69 @@ def main():
 
     ms_per_step = 1000.0 * elapsed_max / args.steps
     value = blends_all * args.steps / elapsed_max
+    out = {
+        "metric": METRIC,
+        "value": round(value, 1),
+        "unit": "blends/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "fp32",
+        "data": "synthetic (seeded random Gaussians / cameras, SURVEY.md §8d)",
+        "config": {"workload": f"{cfg}: {P} Gaussians, {W}x{H}, SH deg 3 + 3-ch language feature, "
+                               f"include_feature train step, 1 view per GPU",
+                   "gaussians": P, "width": W, "height": H, "views": world, "parallelism": f"dp{world} (views)",
+                   "ranks": world, "backend": backend or "none (1 rank)",
+                   "blends_per_step": blends_all, "num_rendered_rank0": nr, "visible_rank0": visible,
+                   "activation_and_loss": "fused" if fused else "torch",
+                   "gradients": "all geometry" if _native.FORCE_GEOMETRY_GRADS else
+                                "as needed: means2D + language feature (geometry frozen, "
+                                "scene/gaussian_model.py:203-217)"},
+        "full": args.full,
+        "step_form": {"eager": "eager launches, one stream",
+                      "pipelined": "eager launches, consecutive views on two streams (the next view's geometry "
+                                   "beside this view's backward" + (", RCCL all-reduce" if world > 1 else "")
+                                   + " and Adam)",
+                      "pipelined_graph": "HIP graphs on two streams: this view's compositing + loss, backward, "
+                                         + ((f"{backend} all-reduce of the language partials and skip flag ("
+                                             + ("in the graph" if collective_capturable() else "between two graphs")
+                                             + ("; RCCL on the step's stream" if rccl.direct_enabled() else "")
+                                             + "), ") if world > 1 and os.environ.get("LSR_PG_DEFER", "1") != "0"
+                                            else (f"{backend} all-reduce ("
+                                                  + ("in the graph" if collective_capturable() else "between two graphs")
+                                                  + "), ") if world > 1 else "") +
+                                         "gradient + Adam + next records' fill pass on one, the next view's "
+                                         "geometry (forward split in two calls) on the other"}[best],
+        "pipelined_graph_rotation": pg_rot,
+        "pipelined_graph_error": pg_error,
+        # the forms this run timed (a plain run: the `value` form alone; None: not timed)
+        "ms_per_step_forms": {n: (round(1000.0 * v / args.steps, 4) if v < 1e29 else None) for n, v in times.items()},
+    }
+
+    def finish():
+        """The outputs of the `value` form's last timed step (--dump-outputs), the result line, teardown."""
+        if args.dump_outputs:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, tensor in snaps[best].items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), tensor.to(torch.float32).cpu().numpy())
+        line = json.dumps(out)
+        print(line, flush=True)
+        if args.json_out:
+            with open(args.json_out, "w") as f:
+                f.write(line + "\n")
+        if world > 1:
+            dist.barrier()
+        if dist.is_initialized():
+            torch.cuda.synchronize()
+            rccl.destroy_default()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
     raster_ms = sum(v["total_ms"] for k, v in prof.items()) / prof_steps
     dom_name = DOMINANT_STAGE
     M = (c["sh_degree"] + 1) ** 2
@@ -740,51 +853,13 @@ def main():
         cpu["pairs_with"] = {"gpu_form": "ms_per_step_all_gradients",
                              "gpu_value": round(blends_all * args.steps / elapsed_all, 1),
                              "gpu_over_cpu": round(blends_all * args.steps / elapsed_all / cpu["value"], 1)}
-    out = {
-        "metric": METRIC,
-        "value": round(value, 1),
-        "unit": "blends/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "fp32",
-        "data": "synthetic (seeded random Gaussians / cameras, SURVEY.md §8d)",
-        "config": {"workload": f"{cfg}: {P} Gaussians, {W}x{H}, SH deg 3 + 3-ch language feature, "
-                               f"include_feature train step, 1 view per GPU",
-                   "gaussians": P, "width": W, "height": H, "views": world, "parallelism": f"dp{world} (views)",
-                   "ranks": world, "backend": backend or "none (1 rank)",
-                   "blends_per_step": blends_all, "num_rendered_rank0": nr, "visible_rank0": visible,
-                   "activation_and_loss": "fused" if fused else "torch",
-                   "gradients": "all geometry" if _native.FORCE_GEOMETRY_GRADS else
-                                "as needed: means2D + language feature (geometry frozen, "
-                                "scene/gaussian_model.py:203-217)"},
+    out.update({
         "ms_per_step_with_sync": round(1000.0 * elapsed_sync / args.steps, 4) if elapsed_sync < 1e29 else None,
         "pipelined_graph_reps_ms": {"reps": [round(x, 4) for x in pg_reps],
                                     "median": round(float(np.median(pg_reps)), 4) if pg_reps else None,
                                     "min": round(min(pg_reps), 4) if pg_reps else None,
                                     "max": round(max(pg_reps), 4) if pg_reps else None},
         "ms_per_step_eager": round(1000.0 * elapsed_eager / args.steps, 4),
-        "step_form": {"eager": "eager launches, one stream",
-                      "pipelined": "eager launches, consecutive views on two streams (the next view's geometry "
-                                   "beside this view's backward" + (", RCCL all-reduce" if world > 1 else "")
-                                   + " and Adam)",
-                      "pipelined_graph": "HIP graphs on two streams: this view's compositing + loss, backward, "
-                                         + ((f"{backend} all-reduce of the language partials and skip flag ("
-                                             + ("in the graph" if collective_capturable() else "between two graphs")
-                                             + ("; RCCL on the step's stream" if rccl.direct_enabled() else "")
-                                             + "), ") if world > 1 and os.environ.get("LSR_PG_DEFER", "1") != "0"
-                                            else (f"{backend} all-reduce ("
-                                                  + ("in the graph" if collective_capturable() else "between two graphs")
-                                                  + "), ") if world > 1 else "") +
-                                         "gradient + Adam + next records' fill pass on one, the next view's "
-                                         "geometry (forward split in two calls) on the other"}[best],
-        "pipelined_graph_rotation": pg_rot,
-        "pipelined_graph_error": pg_error,
-        "ms_per_step_forms": {n: (round(1000.0 * v / args.steps, 4) if v < 1e29 else None) for n, v in times.items()},
         "ms_per_step_all_gradients": round(1000.0 * elapsed_all / args.steps, 4),
         "ms_forward_only": round(1000.0 * elapsed_fwd / args.steps, 4),
         "ms_per_step_rgb": None if rgb_ms is None else round(rgb_ms, 4),
@@ -792,18 +867,8 @@ def main():
         "stages_ms_per_step": {k: round(v["total_ms"] / prof_steps, 4) for k, v in sorted(prof.items())},
         "roofline": roofline,
         "cpu_baseline": cpu,
-    }
-    line = json.dumps(out)
-    print(line, flush=True)
-    if args.json_out:
-        with open(args.json_out, "w") as f:
-            f.write(line + "\n")
-    if world > 1:
-        dist.barrier()
-    if dist.is_initialized():
-        torch.cuda.synchronize()
-        rccl.destroy_default()
-        dist.destroy_process_group()
+    })
+    finish()
 
 
 if __name__ == "__main__":

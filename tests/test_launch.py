@@ -72,14 +72,26 @@ def test_launch_stops_the_others_when_one_rank_fails():
 
 def test_bench_launches_before_touching_the_gpu(monkeypatch):
     """A plain `python bench.py --gpus 2` hands over to the launcher at the top of main(), with its own
-    path and arguments, and exits with the launcher's status."""
+    path and arguments, and exits with the launcher's status.  "Touching the GPU" is any call of
+    torch.cuda._lazy_init (every torch.cuda API and device tensor goes through it), so the check
+    also holds in a process whose earlier tests initialised the device."""
     import bench
     seen = {}
+    was_initialized = torch.cuda.is_initialized()
+    lazy_inits = []
+    real_lazy_init = torch.cuda._lazy_init
+
+    def counted_lazy_init(*a, **k):
+        lazy_inits.append(1)
+        return real_lazy_init(*a, **k)
 
     def fake(argv, n):
         seen["argv"], seen["n"] = list(argv), n
         seen["cuda_initialized"] = torch.cuda.is_initialized()
+        seen["lazy_inits"] = len(lazy_inits)
         return 7
+
+    monkeypatch.setattr(torch.cuda, "_lazy_init", counted_lazy_init)
 
     for k in ("WORLD_SIZE", "RANK"):
         monkeypatch.delenv(k, raising=False)
@@ -90,7 +102,8 @@ def test_bench_launches_before_touching_the_gpu(monkeypatch):
     assert e.value.code == 7
     assert seen["n"] == 2 and seen["argv"][0] == os.path.join(ROOT, "bench.py")
     assert seen["argv"][1:] == ["--gpus", "2", "--steps", "10"]
-    assert not seen["cuda_initialized"]
+    assert seen["lazy_inits"] == 0
+    assert was_initialized or not seen["cuda_initialized"]
 
 
 def test_bench_refuses_a_world_that_is_not_gpus(monkeypatch):

@@ -51,8 +51,14 @@ def test_rgb_sh_conversions(sh_gold):
 
 
 def test_cameras_match_reference():
-    """langsplat_amd.camera reproduces scene/cameras.py:48-57 + utils/graphics_utils.py bit for bit."""
+    """langsplat_amd.camera reproduces scene/cameras.py:48-57 + utils/graphics_utils.py bit for bit,
+    except the camera centre: it is row 3 of torch's fp32 inverse() of the world-view matrix (as in the
+    reference), an LAPACK factorisation whose rounding follows the host's kernels (one host gave
+    2.8284268 where the golden file's gave 2.828427, 1 ulp).  The centre is held to the rounding of
+    that inverse instead -- 8 eps32 of the camera distance 4, the matrix being a rotation and a
+    translation of length 4 -- against the golden value and against the position the camera was put at."""
     g = np.load(os.path.join(GOLD, "cameras.npz"))
+    center_atol = 8 * float(np.finfo(np.float32).eps) * 4.0
     for n in range(int(g["count"])):
         W, H = int(g[f"c{n}_W"]), int(g[f"c{n}_H"])
         views, k = int(g[f"c{n}_views"]), int(g[f"c{n}_k"])
@@ -60,12 +66,14 @@ def test_cameras_match_reference():
         fovx = focal2fov(fov2focal(fovy, H), W)
         assert fovx == float(g[f"c{n}_fovx"])
         th = 2.0 * math.pi * k / views
-        R, T = look_at_origin(np.array([4.0 * math.sin(th), 0.0, -4.0 * math.cos(th)]))
+        position = np.array([4.0 * math.sin(th), 0.0, -4.0 * math.cos(th)])
+        R, T = look_at_origin(position)
         np.testing.assert_array_equal(R, g[f"c{n}_R"])
         cam = make_camera(R, T, fovx, fovy, W, H)
         np.testing.assert_array_equal(cam.world_view_transform.numpy(), g[f"c{n}_world_view"])
         np.testing.assert_array_equal(cam.full_proj_transform.numpy(), g[f"c{n}_full_proj"])
-        np.testing.assert_array_equal(cam.camera_center.numpy(), g[f"c{n}_center"])
+        np.testing.assert_allclose(cam.camera_center.numpy(), g[f"c{n}_center"], rtol=0, atol=center_atol)
+        np.testing.assert_allclose(cam.camera_center.numpy(), position, rtol=0, atol=center_atol)
 
 
 def test_expf_restatement_accuracy():

@@ -1,14 +1,14 @@
 #!/usr/bin/env bash
 # Pipelined-graph A/B: when the next view's geometry starts (run on the GPU box from the repo root)
 set -euo pipefail
-mkdir -p gpurun_out
+out=${LSR_OUT_DIR:-bench_out}
+mkdir -p "$out"
 export LSR_BENCH_RGB=0
 for g in fwd start fwd start; do
-    LSR_PG_GEO=$g timeout -k 10 150 python bench.py --no-cpu-baseline > gpurun_out/pg_$g.log 2>&1
-    python3 - "$g" <<'PY'
+    LSR_PG_GEO=$g timeout -k 10 150 python bench.py --full --no-cpu-baseline > "$out/pg_$g.log" 2>&1
+    python3 - "$out/pg_$g.log" "$g" <<'PY'
 import json, sys
-p = sys.argv[1]
-d = json.loads([l for l in open(f"gpurun_out/pg_{p}.log") if l.startswith("{")][-1])
-print(p, d["ms_per_step_forms"])
+d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
+print(sys.argv[2], d["ms_per_step_forms"])
 PY
 done

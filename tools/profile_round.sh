@@ -2,7 +2,7 @@
 # Profiling recipe for the bench workload of one config (run on the GPU box from the repo root):
 #   kernel trace + stats, then FETCH_SIZE and WRITE_SIZE in separate PMC passes (they do not fit
 #   one pass on gfx950, MI355X_MICROARCH.md "rocprofv3 PMC slots"), then the SQ issue counters, and
-#   the summaries bench.py reads (gpurun_out/<tag>_<cfg>_{summary,valu}.json: copy them into profiles/).
+#   the summaries bench.py reads ($LSR_OUT_DIR (bench_out)/<tag>_<cfg>_{summary,valu}.json: copy them into profiles/).
 #     tools/profile_round.sh r03 C3
 set -euo pipefail
 tag=${1:-rNN}
@@ -11,8 +11,9 @@ root=$(pwd)
 export TMPDIR=/tmp
 export LSR_BENCH_RGB=0  # the RGB step is reported beside the bench line, not profiled here
 export LSR_PIPELINE=0   # serial forms only: overlapped kernels would stretch the per-kernel averages
-out=$root/gpurun_out
-b="$root/bench.py --config $cfg --no-cpu-baseline"
+out=${LSR_OUT_DIR:-$root/bench_out}
+mkdir -p "$out"
+b="$root/bench.py --full --config $cfg --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/${tag}_${cfg}_trace" -o trace -- \
     python3 $b --steps 20 --warmup 5 > "$out/${tag}_${cfg}_trace.log" 2>&1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/${tag}_${cfg}_fetch" -o pmc -- \

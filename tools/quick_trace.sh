@@ -1,7 +1,9 @@
 #!/usr/bin/env bash
-# Kernel trace of a short bench run (run on the GPU box from the repo root): gpurun_out/<tag>_qt/
+# Kernel trace of a short bench run (run on the GPU box from the repo root): $LSR_OUT_DIR (bench_out)/<tag>_qt/
 set -euo pipefail
 tag=${1:-qt}
 export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$(pwd)/gpurun_out/${tag}_qt" -o trace -- \
-    python3 "$(pwd)/bench.py" --steps 20 --warmup 5 --no-cpu-baseline > "gpurun_out/${tag}_qt.log" 2>&1
+out=${LSR_OUT_DIR:-$(pwd)/bench_out}
+mkdir -p "$out"
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$out/${tag}_qt" -o trace -- \
+    python3 "$(pwd)/bench.py" --full --steps 20 --warmup 5 --no-cpu-baseline > "$out/${tag}_qt.log" 2>&1

@@ -1,9 +1,10 @@
-"""Prints step time, value and stage times of bench.py JSON lines (gpurun_out/bench*.log by default)."""
+"""Prints step time, value and stage times of bench.py JSON lines ($LSR_OUT_DIR or bench_out/, bench*.log by default)."""
 import glob
 import json
+import os
 import sys
 
-for f in sys.argv[1:] or sorted(glob.glob("gpurun_out/bench*.log")):
+for f in sys.argv[1:] or sorted(glob.glob(os.path.join(os.environ.get("LSR_OUT_DIR", "bench_out"), "bench*.log"))):
     try:
         d = json.loads(open(f).read().strip().splitlines()[-1])
     except (OSError, ValueError, IndexError) as e:
