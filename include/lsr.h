@@ -510,6 +510,35 @@ int32_t lsr_densification_stats(int32_t P, const int32_t* radii, const float* dL
 int32_t lsr_dist_cuda2(int64_t N, const float* points, float* out_mean_dist, lsr_alloc_fn alloc, void* alloc_user,
                        void* stream);
 
+/* ---- open-vocabulary query ------------------------------------------
+ * What eval/evaluate_iou_loc.py:258-266 does with a rendered language map, for N pixels in ONE
+ * kernel: Autoencoder.decode (autoencoder/model.py:42-46: the decoder's Linears with a ReLU between
+ * them, then x / ||x||, no epsilon), the cosine similarities with n_pos + n_neg unit-norm phrase
+ * embeddings, and OpenCLIPNetwork.get_relevancy (eval/openclip_encoder.py:42-56) for every positive:
+ *     out_relevancy[j, pixel] = min over negatives n of 1 / (1 + exp(10 (s_n - s_j)))
+ * -- get_max_across's (n_phrases, h*w) result of one level.  The decoded D-vectors stay on chip
+ * (out_decoded, for tests and small N, writes them out).  All arithmetic is fp32 (the matrix
+ * products on the exact-fp32 MFMA); no atomics; two calls give bit-identical results.
+ * Supported: input width 3; 1 to 8 layers; every width a multiple of 16, at most 512; n_pos >= 1,
+ * n_neg >= 1, n_pos + n_neg <= 64; weights and phrases 16-byte aligned.  Anything else returns
+ * LSR_ERR_INVALID before any device work.  The call enqueues one kernel on `stream` and does not wait.
+ * N == 0 is valid and enqueues nothing; the pointers (feature, weights, phrases, out_relevancy) must
+ * still be non-NULL.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+typedef struct lsr_query_args {
+    int64_t N;                    /* pixels */
+    const float* feature;         /* the rendered map: channel c of pixel i at feature[c * channel_stride + i * pixel_stride] */
+    int64_t channel_stride, pixel_stride;  /* floats: (HW, 1) = the rasterizer's 3xHxW, (1, 3) = renders_npy's HxWx3 */
+    int32_t n_layers;
+    const int32_t* widths;        /* HOST int32[n_layers], widths[n_layers-1] = D */
+    const float* weights;         /* device: per layer, W (out x in, row-major, nn.Linear's) then b (out), tightly packed */
+    int32_t n_pos, n_neg;
+    const float* phrases;         /* device: (n_pos + n_neg) x D, positives first */
+    float* out_relevancy;         /* device: n_pos x N */
+    float* out_decoded;           /* NULL, or device N x D: the normalised decoded vectors (tests, small N) */
+} lsr_query_args;
+int32_t lsr_query_relevancy(const lsr_query_args* args, void* stream);
+
 size_t lsr_masked_l1_scratch_bytes(int32_t C, int64_t HW);
 int32_t lsr_masked_l1_forward(int32_t C, int64_t HW, const float* pred, const float* gt, const void* mask,
                               int32_t mask_is_float, float* loss, void* scratch, void* stream);

@@ -89,6 +89,13 @@ class LsrKernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_int64), ("total_ms", ctypes.c_double)]
 
 
+class LsrQueryArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int64), ("feature", _vp), ("channel_stride", ctypes.c_int64),
+                ("pixel_stride", ctypes.c_int64), ("n_layers", ctypes.c_int32),
+                ("widths", ctypes.POINTER(ctypes.c_int32)), ("weights", _vp), ("n_pos", ctypes.c_int32),
+                ("n_neg", ctypes.c_int32), ("phrases", _vp), ("out_relevancy", _vp), ("out_decoded", _vp)]
+
+
 ALLOC_FN = ctypes.CFUNCTYPE(_vp, _vp, ctypes.c_int32, ctypes.c_size_t)
 
 # symbol -> (restype, argtypes); must cover every function declared in include/lsr.h
@@ -106,6 +113,7 @@ SIGNATURES = {
     "lsr_backward": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrBackwardArgs), ALLOC_FN, _vp,
                                       _vp]),
     "lsr_mark_visible": (ctypes.c_int32, [ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "lsr_query_relevancy": (ctypes.c_int32, [ctypes.POINTER(LsrQueryArgs), _vp]),
     "lsr_fill_language": (ctypes.c_int32, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_adam_step": (ctypes.c_int32, [ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_int64, _vp]),

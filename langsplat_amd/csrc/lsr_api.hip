@@ -919,6 +919,46 @@ int32_t lsr_graph_launch(void* graph_exec, void* stream_ptr, void* const* wait_e
     return LSR_OK;
 }
 
+int32_t lsr_query_relevancy(const lsr_query_args* a, void* stream_ptr)
+{
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_query_relevancy: null args");
+    if (a->N < 0 || a->N > (int64_t)INT32_MAX * kQPix) return fail(LSR_ERR_INVALID, "lsr_query_relevancy: invalid N");
+    if (a->n_layers < 1 || a->n_layers > kQueryMaxLayers)
+        return fail(LSR_ERR_INVALID, "lsr_query_relevancy: invalid n_layers (1 to 8 layers)");
+    if (!a->widths) return fail(LSR_ERR_INVALID, "lsr_query_relevancy: null widths");
+    QueryParams p{};
+    int off = 0;
+    for (int l = 0; l < a->n_layers; l++) {
+        const int wd = a->widths[l];
+        if (wd < 16 || wd > 512 || wd % 16 != 0)
+            return fail(LSR_ERR_INVALID, "lsr_query_relevancy: invalid width (a multiple of 16, at most 512)");
+        p.widths[l] = wd;
+        p.w_off[l] = off;
+        off += wd * (l ? a->widths[l - 1] : 3) + wd;
+    }
+    if (a->n_pos < 1 || a->n_neg < 1 || a->n_pos + a->n_neg > 64)
+        return fail(LSR_ERR_INVALID, "lsr_query_relevancy: invalid phrase counts (n_pos >= 1, n_neg >= 1, at most 64)");
+    if (!a->feature || !a->weights || !a->phrases || !a->out_relevancy)
+        return fail(LSR_ERR_INVALID, "lsr_query_relevancy: null pointer");
+    if (((reinterpret_cast<uintptr_t>(a->weights) | reinterpret_cast<uintptr_t>(a->phrases)) & 15) != 0)
+        return fail(LSR_ERR_INVALID, "lsr_query_relevancy: weights and phrases must be 16-byte aligned");
+    p.N = a->N;
+    p.feature = a->feature;
+    p.channel_stride = a->channel_stride;
+    p.pixel_stride = a->pixel_stride;
+    p.n_layers = a->n_layers;
+    p.weights = a->weights;
+    p.n_pos = a->n_pos;
+    p.n_neg = a->n_neg;
+    p.phrases = a->phrases;
+    p.out_relevancy = a->out_relevancy;
+    p.out_decoded = a->out_decoded;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;  // read by LSR_TRY (its sync-and-check after the launch): this call has no debug setting
+    LSR_TRY(launch_query(p, stream), "query relevancy");
+    return LSR_OK;
+}
+
 int32_t lsr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                          uint8_t* visible, void* stream_ptr)
 {

@@ -463,6 +463,28 @@ hipError_t launch_decode_language_feature(int H, int W, const int64_t* seg_level
                                           const float* feature_map, float* out, uint8_t* mask, uint32_t* bad,
                                           hipStream_t s);
 
+// lsr_query_relevancy (lsr_query.hip): the decoder MLP, normalisation, phrase similarities and
+// relevancy of kQPix pixels per workgroup
+constexpr int kQPix = 64;
+constexpr int kQueryMaxLayers = 8;
+struct QueryParams {
+    int64_t N;
+    const float* feature;
+    int64_t channel_stride, pixel_stride;
+    int n_layers;
+    int widths[kQueryMaxLayers];
+    int w_off[kQueryMaxLayers];  // floats from `weights` to layer l's W (its bias follows it)
+    const float* weights;
+    int n_pos, n_neg;
+    const float* phrases;
+    float* out_relevancy;
+    float* out_decoded;
+    // LDS plan, filled by launch_query: floats of the activation image, weight rows per staged
+    // chunk (16 / 8 / 4, the most that fits), column stride of a staged weight row
+    int act_floats, kc, ws;
+};
+hipError_t launch_query(QueryParams& p, hipStream_t s);
+
 hipError_t launch_render_forward(const RenderParams& p, int tiles, hipStream_t s);
 hipError_t launch_render_backward(const RenderParams& p, int tiles, hipStream_t s);
 // the fused loss of an empty scene (P == 0: no render forward runs) into p.out_loss
