@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define LSR_ABI_VERSION 17
+#define LSR_ABI_VERSION 18
 
 enum lsr_status {
     LSR_OK = 0,
@@ -201,7 +201,7 @@ typedef struct lsr_forward_args {
      * Whatever the caller orders between the two calls on the stream (e.g. a wait for the feature's
      * update) runs between them, so the two halves can be captured into two HIP graphs replayed on
      * different streams.  The compositing of a composite phase runs at fewer workgroups per CU (6,
-     * leaving wave slots and registers to the other stream; LSR_FWD_SHARE=0: all that fit), which
+     * leaving wave slots and registers to the other stream), which
      * changes no result.  LSR_PHASE_ALL (0): one call does everything. */
     int32_t phase;
 } lsr_forward_args;
@@ -393,10 +393,8 @@ int32_t lsr_debug_bucket_timeline(uint32_t* out, int32_t n);
  * values into out_device[0..3] (a device array of 4 u64): the engine clock the chip ran at meanwhile
  * is 100 (out[3] - out[1]) / (out[2] - out[0]) MHz (tools/clock_probe.py). */
 int32_t lsr_debug_clock_probe(uint64_t* out_device, void* stream);
-/* Measurement aid (ABI 15): a one-wave kernel on `stream` that spins for `microseconds` (at most
- * 1e6) of the constant 100 MHz counter -- a delay between two launches of one stream (the
- * pipelined step's stream phase, LSR_PG_GEO_DELAY_US). */
-int32_t lsr_debug_delay(uint32_t microseconds, void* stream);
+/* (ABI 18 removed ABI 15's delay kernel with the phase-delay experiment it served,
+ * profiles/r06_phase_delays.txt.) */
 /* Host runtime helper (ABI 17): `stream` waits for each of the n_waits events, then the
  * instantiated graph `graph_exec` (a hipGraphExec_t) is launched on it and, if record_event is not
  * null, that event recorded after it -- the stream-A half of a pipelined step's replay in one call

@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LSR_LIB") or os.path.join(_HERE, "liblsr.so")
 
 LSR_BUF_GEOM, LSR_BUF_BINNING, LSR_BUF_IMAGE, LSR_BUF_BACKWARD = 0, 1, 2, 3
-ABI_VERSION = 17
+ABI_VERSION = 18
 ADAM_STEP_WORDS = 66  # include/lsr.h LSR_ADAM_STEP_WORDS
 ADAM_WORD_SKIPPED, ADAM_WORD_LR = 49, 50  # LSR_ADAM_WORD_SKIPPED / LSR_ADAM_WORD_LR
 # lsr_raw_flags (include/lsr.h): inputs are GaussianModel's raw parameters
@@ -136,7 +136,6 @@ SIGNATURES = {
     "lsr_debug_set_spin_limit": (ctypes.c_uint32, [ctypes.c_uint32]),
     "lsr_debug_bucket_timeline": (ctypes.c_int32, [ctypes.POINTER(ctypes.c_uint32), ctypes.c_int32]),
     "lsr_debug_clock_probe": (ctypes.c_int32, [_vp, _vp]),
-    "lsr_debug_delay": (ctypes.c_int32, [ctypes.c_uint32, _vp]),
     "lsr_graph_launch": (ctypes.c_int32, [_vp, _vp, ctypes.POINTER(_vp), ctypes.c_int32, _vp]),
     "lsr_debug_render_stats": (ctypes.c_int32, [ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     "lsr_debug_render_timeline": (ctypes.c_int32, [ctypes.c_int32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_int32]),

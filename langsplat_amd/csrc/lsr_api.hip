@@ -541,7 +541,7 @@ int32_t lsr_forward(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_
     const int guess = hb->depth_passes > 0 ? hb->depth_passes : 4;
     // MSD path: the bucket sort also emits the super-tile entries (into geometry arrays of fixed
     // capacity, so no host value is needed); used below when they fitted
-    const bool fused_emit = !depth_order_uses_pass_count(P) && fused_emit_enabled();
+    const bool fused_emit = !depth_order_uses_pass_count(P);
     LSR_TRY(launch_depth_order(P, guess, L, geom, counters, &hb->stall, stream, debug, fused_emit, 0, placed),
             "depth order");
     hm.mark();
@@ -890,15 +890,6 @@ int32_t lsr_debug_clock_probe(uint64_t* out_device, void* stream_ptr)
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
     const bool debug = false;
     LSR_TRY(launch_clock_probe(out_device, stream), "clock probe");
-    return LSR_OK;
-}
-
-int32_t lsr_debug_delay(uint32_t microseconds, void* stream_ptr)
-{
-    if (microseconds > 1000000u) return fail(LSR_ERR_INVALID, "lsr_debug_delay: at most one second");
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
-    const bool debug = false;
-    LSR_TRY(launch_delay(100u * microseconds, stream), "delay");
     return LSR_OK;
 }
 

@@ -223,10 +223,9 @@ static hipError_t scan_exclusive(const uint32_t* in, uint32_t* out, int n, uint3
 // (scan fault, the tile schedule's class counts) -- so the counters need no memset before the
 // forward -- then publishes counters[0..7] to pinned host memory (system scope) followed by the
 // sequence number the host spins on (one {value, seq} 64-bit slot per counter).
-#ifndef LSR_PUBLISH_THREADS  // the counter reduction's workgroup size (measurement knob): 256 threads find
-#define LSR_PUBLISH_THREADS 256  // a CU beside the pipelined step's render workgroups sooner than 1024
-#endif                           // (C3 step 0.3999-0.4007 vs 0.4008-0.4015 ms, profiles/r05_publish_threads.txt)
-constexpr int kPublishThreads = LSR_PUBLISH_THREADS;
+// The reduction's workgroup size: 256 threads find a CU beside the pipelined step's render workgroups
+// sooner than 1024 (C3 step 0.3999-0.4007 vs 0.4008-0.4015 ms, profiles/r05_publish_threads.txt)
+constexpr int kPublishThreads = 256;
 
 __global__ __launch_bounds__(kPublishThreads) void k_publish_counters(int nb, const uint4* __restrict__ partial,
                                                                       uint32_t* __restrict__ counters,
@@ -742,10 +741,7 @@ static hipError_t radix_sort(const uint32_t* k0, const uint32_t* v0, int n, int 
     const int nblk = (n + tile - 1) / tile;
     const int passes = (total_bits + 7) / 8;
     *passes_out = passes;
-    static const int remap = [] {  // LSR_XCD_REMAP=0: tiles in dispatch order (measurement knob)
-        const char* v = getenv("LSR_XCD_REMAP");
-        return v && v[0] == '0' ? 0 : 1;
-    }();
+    const int remap = 1;  // tiles by XCD, not in dispatch order
     const uint32_t* kin = k0;
     const uint32_t* vin = v0;
     hipError_t e;
@@ -837,10 +833,9 @@ __device__ __forceinline__ uint64_t transpose64(uint64_t x)
 // dense far beyond the average) is sorted by its workgroup in global memory, 1024 keys at a time.
 constexpr int kBucketThreads = 1024;
 constexpr int kBucketWaves = kBucketThreads / 64;
-#ifndef LSR_BUCKET_CAP  // keys a bucket sorts in LDS (a multiple of 1024 up to 8192; measurement knob):
-#define LSR_BUCKET_CAP 8192  // the LDS a bucket workgroup takes, 8 B per key + 8 KB, sets how many
-#endif                       // render workgroups can share its CU while it runs
-constexpr int kBucketCap = LSR_BUCKET_CAP;
+// keys a bucket sorts in LDS (a multiple of 1024 up to 8192): the LDS a bucket workgroup takes, 8 B
+// per key + 8 KB, sets how many render workgroups can share its CU while it runs
+constexpr int kBucketCap = 8192;
 static_assert(kBucketCap % 1024 == 0 && kBucketCap <= 8192, "bucket capacity");
 constexpr int kBucketRounds = kBucketCap / kBucketThreads;  // rounds of 64 keys per wave
 constexpr int64_t kMsdMaxKeys = 2000000;                    // above: 512 buckets (msd_digits)
@@ -1420,20 +1415,15 @@ __device__ __forceinline__ void place_runs(BucketLds& L, const BucketEmit& em, c
 // which the first pass, all passes and the output gathers ended.
 __device__ uint32_t g_bucket_timeline[512 * 8];
 
-#ifndef LSR_BUCKET_MARK_BASE  // measurement knob: the timeline's 4th mark when the entry base is known
-                              // (placed emission: when the entries are listed and ranked)
-#define LSR_BUCKET_MARK_BASE 0
-#endif
-#ifndef LSR_BUCKET_WAVES  // one bucket workgroup per CU: no need to squeeze registers for two
-#define LSR_BUCKET_WAVES 4
-#endif
-#ifndef LSR_BUCKET_WAVES_512  // the 512-bucket sort (measurement knob): 8 = two workgroups per CU, all 512
-#define LSR_BUCKET_WAVES_512 4  // at once, at 64 VGPRs + 56 B of scratch without placed emission: C5 depth
-#endif                          // order 150.9-151.7 against 148.6-148.9 us at 4 (profiles/r05_c5_msd512.txt)
+// Waves per SIMD the sort is compiled for: one bucket workgroup per CU, no need to squeeze registers
+// for two.  The 512-bucket sort at 8 (two workgroups per CU, all 512 at once, at 64 VGPRs + 56 B of
+// scratch without placed emission) measured slower: C5 depth order 150.9-151.7 against 148.6-148.9 us
+// at 4 (profiles/r05_c5_msd512.txt)
+constexpr int kBucketWavesPerEu = 4;
 // kDig buckets (256, or 512 above kMsdMaxKeys).
 template <int kDig>
 __global__ __launch_bounds__(kBucketThreads)
-__attribute__((amdgpu_waves_per_eu(kDig == 512 ? LSR_BUCKET_WAVES_512 : LSR_BUCKET_WAVES, 8)))
+__attribute__((amdgpu_waves_per_eu(kBucketWavesPerEu, 8)))
 void k_depth_bucket_sort(
     int n, uint32_t* __restrict__ keys, uint32_t* __restrict__ ids, const uint32_t* __restrict__ hist_scan, int nblk,
     const uint32_t* __restrict__ kxf, const uint2* __restrict__ rect, uint32_t* __restrict__ sorted_ids,
@@ -1567,7 +1557,7 @@ void k_depth_bucket_sort(
             dig[r] = k & 0xFFu;
             val[r] = ((k >> 8) << kIdxBits) | ((uint32_t)idx & kIdxMask);
         }
-        if (timeline && !LSR_BUCKET_MARK_BASE) {  // measurement only: the keys' arrival
+        if (timeline) {  // measurement only: the keys' arrival
             __builtin_amdgcn_s_waitcnt(0);
             guard.mark(3);
         }
@@ -1690,7 +1680,6 @@ void k_depth_bucket_sort(
                 list_entries(L, em, id, rc, off, 0u, tot);
                 __syncthreads();
                 rank_entries(L, em, (int)tot);
-                if (LSR_BUCKET_MARK_BASE) guard.mark(3);  // measurement only: listed and ranked
                 super_cursors<kDig>(L, em, d, base_s);
                 write_entries(L, em, tot);
                 return;
@@ -1751,7 +1740,6 @@ void k_depth_bucket_sort(
         // workgroup's critical path instead)
         publish_bucket_total(em, d, tot);
         const uint32_t ebase = bucket_entry_base<kDig>(em, d, kxf, L.wsum);
-        if (LSR_BUCKET_MARK_BASE) guard.mark(3);  // measurement only: the entry base known
         if ((uint64_t)ebase + tot > (uint64_t)em.cap) return;  // over capacity: the host re-runs unfused
         // the bucket's entries [ebase, ebase + tot) meet nbl blocks of the super-tile pass: their
         // [super-tile][block] counts in LDS (the free buffer S), then one atomic per non-zero count
@@ -1856,34 +1844,20 @@ static hipError_t allow_bucket_lds()
 // The depth order of P keys: 0 = LSD passes, else the MSD pass's bucket count -- 256 up to
 // kMsdMaxKeys, 512 up to kMsd512MaxKeys (about 8k keys per bucket on average: the LDS sort's
 // capacity), LSD above.  Knobs (measurement / tests, read per call): LSR_DEPTH_LSD=1 forces the LSD
-// passes; LSR_MSD_MAX_KEYS=n and LSR_MSD512_MAX_KEYS=n move the two limits; LSR_MSD_BUCKETS=512
-// takes 512 buckets wherever the MSD pass runs.
+// passes; LSR_MSD_BUCKETS=512 takes 512 buckets wherever the MSD pass runs.
 constexpr int64_t kMsd512MaxKeys = 4200000;
 int msd_digits(int P)
 {
     const char* e = getenv("LSR_DEPTH_LSD");
     if (e && e[0] == '1') return 0;
-    const char* m = getenv("LSR_MSD_MAX_KEYS");
-    const char* m2 = getenv("LSR_MSD512_MAX_KEYS");
     const char* b = getenv("LSR_MSD_BUCKETS");
-    const int64_t lim = m ? (int64_t)atoll(m) : kMsdMaxKeys;
-    const int64_t lim2 = m2 ? (int64_t)atoll(m2) : kMsd512MaxKeys;
-    if (P <= lim) return b && atoi(b) == 512 ? 512 : 256;
-    return P <= lim2 ? 512 : 0;
+    if (P <= kMsdMaxKeys) return b && atoi(b) == 512 ? 512 : 256;
+    return P <= kMsd512MaxKeys ? 512 : 0;
 }
 
 bool depth_order_uses_pass_count(int P) { return msd_digits(P) == 0; }
 
 // ---------------------------------------------------------------- depth order + super-tile counts
-
-bool fused_emit_enabled()
-{
-    static const bool v = [] {
-        const char* e = getenv("LSR_FUSED_EMIT");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
 
 // Keys per thread of the MSD pass's radix tiles: 16 above radix_small's limit, else 8 with 512
 // buckets (C5 depth order 152 -> 139 us against 4, profiles/r05_c5_msd512.txt) and 4 with 256 (the
@@ -1936,10 +1910,7 @@ hipError_t launch_depth_order(int P, int passes, const Layout& L, char* geom, ui
     if (nd) {  // MSD pass + per-bucket LDS sort; `passes` is not used
         hipError_t e = nd == 512 ? allow_bucket_lds<512>() : allow_bucket_lds<256>();
         if (e != hipSuccess) return e;
-        static const int remap = [] {
-            const char* v = getenv("LSR_XCD_REMAP");
-            return v && v[0] == '0' ? 0 : 1;
-        }();
+        const int remap = 1;  // tiles by XCD, not in dispatch order
         const int items = msd_items(P);
         const bool small = items == 4;
         const int nblk = (P + kRadixThreads * items - 1) / (kRadixThreads * items);
@@ -2319,10 +2290,7 @@ __global__ __launch_bounds__(256) void k_bin_count(int S, int sgx, int gx, int g
 // rank in tile l is popcount(column & lanes below) past the lower waves' columns.  The batch's
 // output is up to 64 contiguous runs (one per tile); it is staged in LDS tile-major and written
 // with consecutive lanes on consecutive addresses (batches over kStage instances store directly).
-#ifndef LSR_BIN_STAGE  // staging capacity in instances (LDS: 5 B each); measurement knob
-#define LSR_BIN_STAGE 4096
-#endif
-constexpr int kStage = LSR_BIN_STAGE;
+constexpr int kStage = 4096;  // staging capacity in instances (LDS: 5 B each)
 
 // k_bin_count with the segment setup folded in, for a super-tile sort of ONE radix pass (S <= 256
 // super-tiles): the super-tile ranges are then the digit starts of the scanned [digit][block]
@@ -2646,10 +2614,7 @@ hipError_t launch_binning(int P, int64_t R, const Layout& L, char* geom, char* i
                                 (int)L.super_hist_words, reinterpret_cast<uint32_t*>(geom + L.super_hist_status),
                                 nullptr, stall, s, debug)) != hipSuccess)
             return e;
-        static const int remap = [] {
-            const char* v = getenv("LSR_XCD_REMAP");
-            return v && v[0] == '0' ? 0 : 1;
-        }();
+        const int remap = 1;  // tiles by XCD, not in dispatch order
         const int nblk = (int)((E + kSuperHistBlock - 1) / kSuperHistBlock);
         hipLaunchKernelGGL((k_radix_scatter<4, false>), dim3(nblk), dim3(kRadixThreads), 0, s, k0, v0, (int)E, 0,
                            L.super_bits, (const uint32_t*)bin_hist_scan, nblk, kB, vB, (const uint32_t*)nullptr,

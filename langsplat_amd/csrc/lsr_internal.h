@@ -38,15 +38,9 @@ constexpr int kCntWords = kCntSlots + 2 * kWorkClasses;
 // feature sums) before list entries kSplitChunk, 2 kSplitChunk, ... (up to entry 1024 - kSplitChunk)
 // of a tile it is still compositing (in the tile's own kSplitMax slots), so the backward can replay
 // a long tile as up to kSplitItems independent work items of <= kSplitChunk entries each (the last
-// one: the rest) instead of one long serial chain.  LSR_SPLIT_CHUNK=128 (round 6, measured and not
-// the default: each wave records the boundary inside a 256-entry batch mid-walk) halved the items
-// but cost more than it saved -- C3 render backward 141 -> 152 us, forward 125 -> 132 us, pipelined
-// step 0.400 -> 0.465 ms (profiles/r06_split128_ab.txt).
-#ifndef LSR_SPLIT_CHUNK
-#define LSR_SPLIT_CHUNK 256
-#endif
-constexpr int kSplitChunk = LSR_SPLIT_CHUNK;
-static_assert(kSplitChunk == 128 || kSplitChunk == 256, "split chunks of 128 or 256 list entries");
+// one: the rest) instead of one long serial chain.  Chunks of 128 entries were measured in round 6
+// and not kept (profiles/r06_split128_ab.txt).
+constexpr int kSplitChunk = 256;  // one batch of the forward's walk (kTilePixels)
 constexpr int kSplitMax = 1024 / kSplitChunk - 1;  // recorded boundaries per tile
 constexpr int kSplitItems = kSplitMax + 1;  // backward work items per tile
 constexpr int kSplitVals = 8;               // per pixel {T, feature (3)}, {colour (3), -}
@@ -55,10 +49,7 @@ constexpr int kSplitSlots = kSplitMax + 1;  // per tile: the boundaries' states,
 constexpr int kRadixThreads = 256;
 // preprocess workgroups: the SH staging takes 4 (3M + 1) bytes of LDS per thread, so 128-thread
 // blocks let more of them share a CU and overlap one block's loads with another's arithmetic
-#ifndef LSR_PRE_THREADS
-#define LSR_PRE_THREADS 128
-#endif
-constexpr int kPreThreads = LSR_PRE_THREADS;
+constexpr int kPreThreads = 128;
 constexpr int kSuper = 8;          // super-tile = kSuper x kSuper tiles (64-bit tile masks)
 constexpr int kSegEntries = 512;   // super-tile list entries per binning workgroup
 constexpr int kGradStride = 16;                          // floats per Gaussian grad record
@@ -336,8 +327,6 @@ hipError_t launch_depth_order(int P, int passes, const Layout& L, char* geom, ui
 // ignores `passes`; true (large P): LSD passes, `passes` must cover the visible key range
 bool depth_order_uses_pass_count(int P);
 int msd_digits(int P);  // the depth order's MSD buckets (256 / 512), 0: LSD passes
-// LSR_FUSED_EMIT=0 turns the fused super-tile emission off (measurement knob, read once)
-bool fused_emit_enabled();
 // placed emission: the fused emission writes every entry at its super-tile-major position, so the
 // binning's super-tile pass (scan + scatter) is not launched.  Needs <= 256 super-tiles.  Default:
 // on for a whole forward, off for the split geometry phase (whose kernels run beside the previous
@@ -493,6 +482,5 @@ hipError_t render_stats_read(unsigned long long* out, int n);  // reads and clea
 hipError_t render_timeline_read(uint32_t* out, int kernel, int n);
 hipError_t bucket_timeline_read(uint32_t* out, int n);  // LSR_BUCKET_TIMELINE=1 records (k_depth_bucket_sort)
 hipError_t launch_clock_probe(uint64_t* out, hipStream_t s);  // lsr_debug_clock_probe
-hipError_t launch_delay(uint32_t ticks, hipStream_t s);        // lsr_debug_delay
 
 }  // namespace lsr

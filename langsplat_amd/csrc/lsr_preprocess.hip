@@ -161,15 +161,8 @@ static size_t sh_lds_bytes(const float* shs, const float* shs_rest, int M)
 // count against another
 enum ShMode { kShLds = 0, kShDma = 1, kShDirect = 2 };
 
-#ifndef LSR_PRE_NT  // 1: the SH rows (192 of the ~250 B read per Gaussian) loaded non-temporally
-#define LSR_PRE_NT 0
-#endif
-#ifndef LSR_PRE_DIRECT_WAVES  // measurement knob: occupancy target of the kShDirect instance (0: none)
-#define LSR_PRE_DIRECT_WAVES 0
-#endif
 template <int kSh>
-__global__ __launch_bounds__(kPreThreads) __attribute__((amdgpu_waves_per_eu(
-    kSh == kShDirect && LSR_PRE_DIRECT_WAVES > 0 ? LSR_PRE_DIRECT_WAVES : 1))) void k_preprocess(PreprocessParams p)
+__global__ __launch_bounds__(kPreThreads) void k_preprocess(PreprocessParams p)
 {
     extern __shared__ float s_sh[];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -229,7 +222,7 @@ __global__ __launch_bounds__(kPreThreads) __attribute__((amdgpu_waves_per_eu(
         const char* row = reinterpret_cast<const char*>(p.shs_rest) + ic * 180u;
 #pragma unroll
         for (int k = 0; k < 11; k++) {
-            const float4 v = LSR_PRE_NT ? load_f4u_nt(row + 16 * k) : load_f4u(row + 16 * k);
+            const float4 v = load_f4u(row + 16 * k);
             rr[4 * k] = v.x;
             rr[4 * k + 1] = v.y;
             rr[4 * k + 2] = v.z;
@@ -296,12 +289,6 @@ __global__ __launch_bounds__(kPreThreads) __attribute__((amdgpu_waves_per_eu(
             rgb[ch] = fmaxf(v, 0.0f);
         }
     };
-#ifndef LSR_PRE_EARLY_SH  // measurement knob: kShDirect evaluates the SH before the projection
-#define LSR_PRE_EARLY_SH 0
-#endif
-    // (its 45 registers free before the projection arithmetic; culled Gaussians evaluate it too)
-    constexpr bool early = kSh == kShDirect && LSR_PRE_EARLY_SH;
-    if (early && live) eval_rgb();
     // per-thread contributions to the block partials: tile instances, super-tile entries, depth key
     uint32_t my_tiles = 0, my_supers = 0, my_key = 0xFFFFFFFFu, my_err = 0;
     bool vis = false;  // reached the end of the block below (else culled: written after it)
@@ -344,7 +331,7 @@ __global__ __launch_bounds__(kPreThreads) __attribute__((amdgpu_waves_per_eu(
     if (area == 0) break;
 
     if (p.shs) {
-        if (!early) eval_rgb();
+        eval_rgb();
     } else {
         rgb[0] = p.colors[3 * i];
         rgb[1] = p.colors[3 * i + 1];
@@ -481,11 +468,7 @@ hipError_t launch_preprocess(const PreprocessParams& p, hipStream_t s)
     if (p.P == 0) return hipSuccess;
     if (p.P >= (1 << 27)) return hipErrorInvalidValue;  // k_preprocess's 32-bit row offsets
     size_t lds = sh_lds_bytes(p.shs, p.shs_rest, p.M);
-    static const int direct = [] {  // measurement knob: LSR_PRE_SH=dma (LDS-DMA staging instead)
-        const char* v = getenv("LSR_PRE_SH");
-        return v && v[0] == 'd' && v[1] == 'm' ? 0 : 1;
-    }();
-    const int mode = !sh_dma(p.shs, p.shs_rest, p.M) ? kShLds : (direct && p.M == 16 && p.D <= 3 && (int64_t)p.P * 180 < (int64_t)1 << 31 && !p.cov_pre && p.include_feature && p.lang)
+    const int mode = !sh_dma(p.shs, p.shs_rest, p.M) ? kShLds : (p.M == 16 && p.D <= 3 && (int64_t)p.P * 180 < (int64_t)1 << 31 && !p.cov_pre && p.include_feature && p.lang)
                    ? kShDirect : kShDma;
     const void* fn = mode == kShDirect ? (const void*)k_preprocess<kShDirect>
                    : mode == kShDma ? (const void*)k_preprocess<kShDma> : (const void*)k_preprocess<kShLds>;

@@ -107,23 +107,20 @@ __device__ __forceinline__ uint32_t entry_cover(float x, float y, float a, float
 }
 
 // Compacts the batch slots [0, cnt) whose cover mask meets `bits` (the wave's blocks) into
-// list[0, n) as LDS byte offsets 16 e of their 16-B records; returns n.
-// n_mid: how many of them lie in slots [0, kSplitChunk) (the walk's split-replay boundary inside the
-// batch when kSplitChunk < 256).
-__device__ __forceinline__ int wave_compact(const uint8_t* sM, int cnt, uint32_t bits, int lane, uint16_t* list,
-                                            int& n_mid)
+// list[0, n) as LDS byte offsets 16 e of their 16-B records; returns n.  cnt <= kTilePixels: at most
+// four rounds, unrolled.
+__device__ __forceinline__ int wave_compact(const uint8_t* sM, int cnt, uint32_t bits, int lane, uint16_t* list)
 {
     int n = 0;
-    n_mid = 0;
-    for (int r = 0; r < cnt; r += 64) {
+#pragma unroll
+    for (int r = 0; r < kTilePixels; r += 64) {
+        if (r >= cnt) break;
         const int e = r + lane;
         const bool ov = e < cnt && (sM[e] & bits) != 0u;
         const uint64_t m = __ballot(ov);
         if (ov) list[n + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(16 * e);
         n += __popcll(m);
-        if (r + 64 == kSplitChunk) n_mid = n;
     }
-    if (cnt <= kSplitChunk) n_mid = n;
     return n;
 }
 
@@ -218,7 +215,7 @@ __device__ __forceinline__ void timeline_put(int kernel, uint64_t t0, int tile, 
     o[10] = rel[4] | (rel[5] << 16);
 }
 
-// Wave priority by launch position (LSR_PRIO=0: off).  A tile's compositing is one serial chain
+// Wave priority by launch position.  A tile's compositing is one serial chain
 // per pixel, so the kernel can end no earlier than its longest tile's chain, and the longest tiles
 // (launched first) share their SIMDs with up to 7 other waves.  Raising the first-launched
 // workgroups' priority was meant to let those chains run closer to their own latency; measured at
@@ -488,29 +485,14 @@ __device__ float render_empty_tiles(const RenderParams& p, int j, int M)
 // 7 waves per SIMD (<= 72 VGPRs): the fused-loss variant's rare bounded-wait fallback
 // (loss_block_publish) would otherwise raise its register count to 83 (6 waves); with the bound the
 // compiler spills three values, stored once per workgroup and reloaded on that path only.
-#ifndef LSR_FWD_WAVES  // waves per SIMD the forward is compiled for (measurement knob)
-#define LSR_FWD_WAVES 7
-#endif
-#ifndef LSR_FWD_QUAD  // 1: four list entries per walk step (two packed exp chains), 0: two
-#define LSR_FWD_QUAD 0
-#endif
-#if LSR_FWD_QUAD && LSR_SPLIT_CHUNK != 256
-#error "the four-entry walk records split-replay states at batch starts only: LSR_SPLIT_CHUNK=256"
-#endif
-#ifndef LSR_FWD_PREFETCH  // 1: the next batch's records are gathered during the walk
-#define LSR_FWD_PREFETCH 0
-#endif
-#ifndef LSR_BWD_WORK_ORDER  // 1: the backward's items ordered by the forward's walk counts, 0: by entries
-#define LSR_BWD_WORK_ORDER 1
-#endif
-#ifndef LSR_FWD_STATE_SKIP  // 1: split-replay states stored only for the pixels the backward starts from them
-#define LSR_FWD_STATE_SKIP 1
-#endif
+constexpr int kFwdWaves = 7;  // waves per SIMD the forward is compiled for
 template <bool kStats, bool kFeat, bool kLoss>
-__global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(RenderParams p)
+__global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(RenderParams p)
 {
     const uint64_t t_start = kStats ? wall_clock64() : 0;
     constexpr int kThreads = kTilePixels;
+    // one batch of the walk = one split-replay chunk: boundary states are recorded at batch starts only
+    static_assert(kSplitChunk == kTilePixels, "the forward records split-replay states at batch starts");
     __shared__ float4 sA[kThreads];  // x, y, -0.5 conic.x, -0.5 conic.z
     __shared__ float4 sB[kThreads];  // conic.y, opacity, power cutoff, -
     __shared__ float4 sC[kThreads];  // r, g, b, f0
@@ -522,10 +504,9 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
     // reads the next step's one step ahead (up to slot n + 7)
     __shared__ __attribute__((aligned(8))) uint16_t sL[kThreads / 64][kThreads + 8];
     __shared__ uint32_t s_last;
-    // LSR_BWD_WORK_ORDER: per wave, the list slots its walk visited in batches 0, 1, 2 and from 3 on
-    // (one batch = one split-replay chunk): what the backward's item of that chunk visits in this wave
-    constexpr bool kWorkOrder = LSR_BWD_WORK_ORDER && kSplitChunk == kThreads;
-    __shared__ uint32_t s_walk[kWorkOrder ? kThreads / 64 : 1][kSplitItems];
+    // per wave, the list slots its walk visited in batches 0, 1, 2 and from 3 on (one batch = one
+    // split-replay chunk): what the backward's item of that chunk visits in this wave
+    __shared__ uint32_t s_walk[kThreads / 64][kSplitItems];
     uint32_t wk0 = 0, wk1 = 0, wk2 = 0, wk3 = 0;  // (wave-uniform)
     uint32_t bi = 0;                              // batch index
 
@@ -571,22 +552,10 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
     uint32_t nrec = 0;  // split replay: boundaries recorded (kSplitChunk, 2 kSplitChunk, ... up to kSplitMax; uniform)
 
     FwdPixel q{inside ? 1.0f : -1.0f, make_f2(0.f, 0.f), make_f2(0.f, 0.f), make_f2(0.f, 0.f), 0u, 0u};
-    // Software pipeline over the batches: a batch's records are gathered during the previous batch's
-    // walk (into registers the walk leaves free), and the point_list ids one batch earlier still, so
-    // a batch's load phase waits for no memory round trip (the timeline showed ~9 us of load phase per
-    // batch on the heaviest tiles, a quarter of their time, mostly the gather's latency)
+    // a batch's point_list ids are loaded during the previous batch's walk, so its load phase waits
+    // for one memory round trip (the record gather), not two
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
-#if LSR_FWD_PREFETCH
-    if (start + t < end) {
-        const uint32_t g = p.point_list[start + t];
-        a = p.record[3 * (size_t)g];
-        b = p.record[3 * (size_t)g + 1];
-        c = p.record[3 * (size_t)g + 2];
-    }
-    uint32_t g_next = start + kThreads + t < end ? p.point_list[start + kThreads + t] : 0u;
-#else
     uint32_t g_next = start + t < end ? p.point_list[start + t] : 0u;
-#endif
     for (uint32_t base = start; base < end; base += kThreads) {
         const bool all_done = __syncthreads_count(q.T < 0.0f) == kThreads;
         if (kStats && base != start) ph.lap(ph.walk);
@@ -601,7 +570,6 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             ph.st[3] = wall_clock64();
         }
-#if !LSR_FWD_PREFETCH
         a = b = c = make_float4(0.f, 0.f, 0.f, 0.f);
         if (idx < end) {
             const uint32_t g = g_next;
@@ -609,29 +577,23 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
             b = p.record[3 * (size_t)g + 1];
             c = p.record[3 * (size_t)g + 2];
         }
-#endif
         if (kStats && base == start) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             ph.st[4] = wall_clock64();
         }
-        // split-replay state of each pixel at list entry e (e = base - start here, or the middle of the
-        // batch, below): slot e / kSplitChunk - 1, two float4 per pixel
-        auto record_state = [&](uint32_t slot) {
-            float4* st = reinterpret_cast<float4*>(p.split_pool) + ((size_t)tile * kSplitSlots + slot) * (2 * kThreads);
-            // A pixel already done (or outside the image: T < 0) has its last contributor before the
-            // boundary, so the backward never starts it from here: no store (LSR_FWD_STATE_SKIP=0 stores)
-            if (!LSR_FWD_STATE_SKIP || q.T > 0.0f) {
-                st[2 * t] = make_float4(q.T, q.C2F0.y, q.F12.x, q.F12.y);
-                if (p.split_color) st[2 * t + 1] = make_float4(q.C01.x, q.C01.y, q.C2F0.x, 0.0f);
-            }
-        };
         if (p.split_pool && base != start && base - start <= (uint32_t)(kSplitMax * kSplitChunk)) {
             // split replay: every pixel's state before list entry 256 j while some pixel composites,
             // two float4 per pixel in the tile's own slot j - 1 (a grid-wide slot counter cost ~40 us
-            // of contended cross-XCD atomics); a pixel already done is never started from here
+            // of contended cross-XCD atomics)
             // {T, feature sums}, then {colour sums} unless no colour gradient can follow (the language
             // step: half the state traffic)
-            record_state(nrec);
+            float4* st = reinterpret_cast<float4*>(p.split_pool) + ((size_t)tile * kSplitSlots + nrec) * (2 * kThreads);
+            // A pixel already done (or outside the image: T < 0) has its last contributor before the
+            // boundary, so the backward never starts it from here: no store
+            if (q.T > 0.0f) {
+                st[2 * t] = make_float4(q.T, q.C2F0.y, q.F12.x, q.F12.y);
+                if (p.split_color) st[2 * t + 1] = make_float4(q.C01.x, q.C01.y, q.C2F0.x, 0.0f);
+            }
             nrec++;
         }
         if (idx < end) {
@@ -653,28 +615,11 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
             }
         }
         const int cnt = (int)min((uint32_t)kThreads, end - base);
-        int n_mid_raw;
-        const int n = __builtin_amdgcn_readfirstlane(
-            wave_compact(sM, cnt, 1u << wave, lane, sL[wave], n_mid_raw));
-        const int n_mid = __builtin_amdgcn_readfirstlane(n_mid_raw);
-        // the boundary in the middle of the batch (kSplitChunk < 256), recorded by each wave when its
-        // walk reaches it: uniform over the workgroup
-        const bool mid = kSplitChunk < kThreads && p.split_pool && cnt > kSplitChunk &&
-                         base - start + kSplitChunk <= (uint32_t)(kSplitMax * kSplitChunk);
+        const int n = __builtin_amdgcn_readfirstlane(wave_compact(sM, cnt, 1u << wave, lane, sL[wave]));
         if (lane < 4) sL[wave][n + lane] = 0;
         __syncthreads();  // list visible to the wave's other lanes
         if (kStats) ph.lap(ph.compact);
-#if LSR_FWD_PREFETCH
-        if (idx + kThreads < end) {  // the next batch's records, and the ids of the one after
-            const uint32_t g = g_next;
-            a = p.record[3 * (size_t)g];
-            b = p.record[3 * (size_t)g + 1];
-            c = p.record[3 * (size_t)g + 2];
-        }
-        if (idx + 2 * kThreads < end) g_next = p.point_list[idx + 2 * kThreads];
-#else
         if (idx + kThreads < end) g_next = p.point_list[idx + kThreads];
-#endif
         const uint32_t lb16 = 16u * (base - start + 1u);  // 16 x (list index of slot 0 + 1)
         const char* const cA = reinterpret_cast<const char*>(sA);
         const char* const cB = reinterpret_cast<const char*>(sB);
@@ -711,75 +656,31 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
         // one basic block per step (the blends have no branches, the wave's "all done" test closes the
         // iteration), so the next step's offset read stays beside this step's record reads
         int i = 0;
-#if LSR_FWD_QUAD
-        // four entries per step: two independent packed exp chains, so a wave has twice the
-        // instruction-level parallelism between its dependent operations
-        const uint2* const sL4 = reinterpret_cast<const uint2*>(sL[wave]);
-        uint2 oo = sL4[0];
+        // the pairs of list slots [0, n) (a last odd slot alone)
+        const uint32_t* const sL2 = reinterpret_cast<const uint32_t*>(sL[wave]);
+        uint32_t oo = sL2[0];
         if (n > 0 && __ballot(q.T > 0.0f) != 0ull) do {
-            const uint32_t o0 = oo.x & 0xFFFFu, o1 = oo.x >> 16, o2 = oo.y & 0xFFFFu, o3 = oo.y >> 16;
-            oo = sL4[(i >> 2) + 1];  // slots i + 4 .. i + 7 (<= n + 7)
-            float al0, al1, al2, al3;
-            bool ok0, ok1, ok2, ok3;
+            const uint32_t o0 = oo & 0xFFFFu, o1 = oo >> 16;
+            oo = sL2[(i >> 1) + 1];  // slots i + 2, i + 3 (<= n + 1)
+            float al0, al1;
+            bool ok0, ok1;
             pair_alpha(o0, o1, i + 1 < n, al0, al1, ok0, ok1);
-            pair_alpha(o2, o3, i + 3 < n, al2, al3, ok2, ok3);
-            ok2 = ok2 && i + 2 < n;
             blend_at(al0, ok0, o0);
             blend_at(al1, ok1, o1);
-            blend_at(al2, ok2, o2);
-            blend_at(al3, ok3, o3);
             // the next offsets are this iteration's value: the compiler may not defer their read to
             // the next iteration's start (where the record reads would wait behind it)
-            asm volatile("" : "+v"(oo.x), "+v"(oo.y));
-            i += 4;
+            asm volatile("" : "+v"(oo));
+            i += 2;
         } while (i < n && __ballot(q.T > 0.0f) != 0ull);
-#else
-        const uint32_t* const sL2 = reinterpret_cast<const uint32_t*>(sL[wave]);
-        // the pairs of list slots [i, lim), i even (a last odd slot alone)
-        auto walk = [&](int lim) {
-            uint32_t oo = sL2[i >> 1];
-            if (i < lim && __ballot(q.T > 0.0f) != 0ull) do {
-                const uint32_t o0 = oo & 0xFFFFu, o1 = oo >> 16;
-                oo = sL2[(i >> 1) + 1];  // slots i + 2, i + 3 (<= n + 1)
-                float al0, al1;
-                bool ok0, ok1;
-                pair_alpha(o0, o1, i + 1 < lim, al0, al1, ok0, ok1);
-                blend_at(al0, ok0, o0);
-                blend_at(al1, ok1, o1);
-                asm volatile("" : "+v"(oo));
-                i += 2;
-            } while (i < lim && __ballot(q.T > 0.0f) != 0ull);
-        };
-        if (!mid) {
-            walk(n);
-        } else {
-            // the wave's entries before the batch's middle, its pixels' state there, the rest
-            walk(n_mid);
-            record_state(nrec);
-            i = n_mid;
-            if ((n_mid & 1) && n_mid < n && __ballot(q.T > 0.0f) != 0ull) {  // slot n_mid alone
-                const uint32_t o0 = sL[wave][n_mid];
-                float al0, al1;
-                bool ok0, ok1;
-                pair_alpha(o0, o0, false, al0, al1, ok0, ok1);
-                blend_at(al0, ok0, o0);
-            }
-            i = (n_mid + 1) & ~1;
-            walk(n);
-        }
-        if (mid) nrec++;
-#endif
-        if (kWorkOrder) {
-            const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(min(i, n));
-            if (bi == 0) wk0 = wv;
-            else if (bi == 1) wk1 = wv;
-            else if (bi == 2) wk2 = wv;
-            else wk3 += wv;
-            bi++;
-        }
+        const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(min(i, n));
+        if (bi == 0) wk0 = wv;
+        else if (bi == 1) wk1 = wv;
+        else if (bi == 2) wk2 = wv;
+        else wk3 += wv;
+        bi++;
         if (lo != 0xFFFFFFFFu) q.last16 = lb16 + lo;
     }
-    if (kWorkOrder && lane == 0) {
+    if (lane == 0) {
         static_assert(kSplitItems == 4, "four walk counters per wave");
         s_walk[wave][0] = wk0;
         s_walk[wave][1] = wk1;
@@ -798,10 +699,8 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
     // s_last (split replay), each appended to the class of its length
     const uint32_t maxl = s_last;
     const uint32_t nsplit = p.split_pool && maxl > 0 ? min(nrec, (maxl - 1u) / (uint32_t)kSplitChunk) : 0u;
-    // the backward's items into the longest-first class lists: the tile's full 256-entry chunks with
-    // ONE returning atomic on their class (+nsplit), its last chunk with another, in parallel (thread
-    // 1): an atomic per chunk put every heavy tile's chunks on one hot counter across the XCDs
-    if (kWorkOrder && p.sched_counts && maxl > 0 && !p.no_bwd) {
+    // the backward's items into the longest-first class lists
+    if (p.sched_counts && maxl > 0 && !p.no_bwd) {
         // one item per thread t <= nsplit, classed by its work: the walk's visits in the chunk's batch
         // (the last item: its batches' visits summed) in the wave that visited most, plus a fixed share
         // for its record loads and flush.  The class lists stay longest first by what the backward
@@ -821,24 +720,12 @@ __global__ __launch_bounds__(kTilePixels, LSR_FWD_WAVES) void k_render_forward(R
             schedule_tile(p.sched_counts + kCntBwdClass, p.sched_lists + (size_t)kWorkClasses * T,
                           kSplitItems * T, kSplitItems * tile + t, 32u + w);
         }
-    } else if (t < 2 && p.sched_counts && maxl > 0 && !p.no_bwd) {
-        uint32_t* counts = p.sched_counts + kCntBwdClass;
-        uint32_t* lists = p.sched_lists + (size_t)kWorkClasses * T;
-        const size_t stride = (size_t)kSplitItems * T;
-        if (t == 0 && p.split_pool) p.split_desc[tile] = make_uint4(nsplit, maxl, 0u, 0u);
-        if (t == 0 && nsplit > 0) {
-            const int c = work_class((uint32_t)kSplitChunk);
-            const uint32_t base = atomicAdd(&counts[c], nsplit);
-            for (uint32_t k = 0; k < nsplit; k++) lists[(size_t)c * stride + base + k] = kSplitItems * tile + k;
-        }
-        if (t == (nsplit > 0 ? 1 : 0))
-            schedule_tile(counts, lists, (int)stride, kSplitItems * tile + (int)nsplit, maxl - nsplit * kSplitChunk);
     }
     // the final sums, for the backward's running `acc` at each boundary, (C_final - C_front) / T_b: a
     // store here (the tile's extra slot), the arithmetic in the backward -- normalising the slots in
     // place needed a load round trip at the end of every long tile, i.e. on the kernel's critical path
     // (read only for pixels that composite past the first boundary: q.last > hi >= kSplitChunk)
-    if (nsplit > 0 && (!LSR_FWD_STATE_SKIP || qlast > (uint32_t)kSplitChunk)) {
+    if (nsplit > 0 && qlast > (uint32_t)kSplitChunk) {
         float4* fin = reinterpret_cast<float4*>(p.split_pool) + ((size_t)tile * kSplitSlots + kSplitMax) * (2 * kThreads);
         fin[2 * t] = make_float4(q.C2F0.y, q.F12.x, q.F12.y, 0.0f);
         if (p.split_color) fin[2 * t + 1] = make_float4(q.C01.x, q.C01.y, q.C2F0.x, 0.0f);
@@ -928,79 +815,6 @@ static bool render_stats_on()
     return v;
 }
 
-// LSR_PRIO=0 turns the launch-position wave priority off (measurement aid)
-static int prio_levels()
-{
-    static const int v = [] {
-        const char* e = getenv("LSR_PRIO");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    return v;
-}
-
-// LSR_DEBUG_GRID=n launches only the first n workgroups of each render kernel (measurement aid for
-// the timeline: a long tile's time alone vs among others; the outputs are then incomplete)
-static int debug_grid(int tiles)
-{
-    static const int v = [] {
-        const char* e = getenv("LSR_DEBUG_GRID");
-        return e ? atoi(e) : 0;
-    }();
-    return v > 0 && v < tiles ? v : tiles;
-}
-
-// LSR_FWD_PAD=bytes adds dynamic LDS to every forward workgroup, i.e. caps its workgroups per CU
-// (measurement aid: how the longest tiles' chains respond to sharing their CU)
-static size_t forward_pad()
-{
-    static const size_t v = [] {
-        const char* e = getenv("LSR_FWD_PAD");
-        return e ? (size_t)atoi(e) : (size_t)0;
-    }();
-    return v;
-}
-
-// LSR_BWD_PAD=bytes: the same for the backward
-static size_t backward_pad()
-{
-    static const size_t v = [] {
-        const char* e = getenv("LSR_BWD_PAD");
-        return e ? (size_t)atoi(e) : (size_t)0;
-    }();
-    return v;
-}
-
-// LSR_SPLIT=0: no split replay (the forward records no boundary state, the backward replays each
-// tile as one work item; measurement aid)
-static bool split_replay()
-{
-    static const bool v = [] {
-        const char* e = getenv("LSR_SPLIT");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// LSR_ORDER=0 launches the tiles in tile order (measurement aid)
-static bool scheduled()
-{
-    static const bool v = [] {
-        const char* e = getenv("LSR_ORDER");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// LSR_SPLIT_COLOR=1 stores the colour half of the split-replay states even under
-// LSR_FWD_NO_COLOR_GRAD (measurement aid: same-box A/B of the state traffic)
-static bool split_color_forced()
-{
-    static const bool v = [] {
-        const char* e = getenv("LSR_SPLIT_COLOR");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
 
 // Workgroups per CU of the render kernels while another stream's kernels run beside them (the
 // pipelined step, §5b): the backward at 7 of 8 and the forward at 6 of 7, so the geometry stream
@@ -1013,36 +827,25 @@ constexpr size_t kCuLds = 160 * 1024;
 // Dynamic LDS that leaves room for exactly `wgs` workgroups of kernel fn per CU (0 if its static
 // LDS already allows no more), rounded to 1 KiB: the allocation granularity must not push the
 // last workgroup out.
-#ifndef LSR_PAD_MIN
-#define LSR_PAD_MIN 0
-#endif
-static size_t occupancy_pad(const void* fn, int wgs, const char* what)
+static size_t occupancy_pad(const void* fn, int wgs)
 {
     hipFuncAttributes at{};
     size_t stat = 20 * 1024;
     if (hipFuncGetAttributes(&at, fn) == hipSuccess) stat = at.sharedSizeBytes;
-    // wgs of them fit, one more does not: the largest such 1 KiB multiple, or (LSR_PAD_MIN=1) the
-    // smallest, which leaves the most LDS to the other stream's workgroups
-    const size_t per = LSR_PAD_MIN ? ((kCuLds / (wgs + 1) + 1024) & ~(size_t)1023) : (kCuLds / wgs) & ~(size_t)1023;
-    const size_t pad = per > stat && per * (wgs + 1) > kCuLds ? per - stat : 0;
-    if (getenv("LSR_SHARE_PRINT")) fprintf(stderr, "lsr: %s static LDS %zu pad %zu\n", what, stat, pad);
-    return pad;
+    // wgs of them fit, one more does not: the largest such 1 KiB multiple (the smallest, which leaves
+    // the most LDS to the other stream's workgroups, measured slower: profiles/r05_padmin.txt)
+    const size_t per = (kCuLds / wgs) & ~(size_t)1023;
+    return per > stat && per * (wgs + 1) > kCuLds ? per - stat : 0;
 }
-// The forward's LDS pad (variants: 0 feature + fused loss, 1 feature, 2 colour only): LSR_FWD_PAD
-// when set, else in a composite phase (another stream beside it) the kSharedWgsFwd cap unless
-// LSR_FWD_SHARE=0, else none.
+// The forward's LDS pad (variants: 0 feature + fused loss, 1 feature, 2 colour only): in a composite
+// phase (another stream beside it) the kSharedWgsFwd cap, else none.
 static size_t forward_launch_pad(const RenderParams& p, int variant)
 {
-    static const bool explicit_pad = getenv("LSR_FWD_PAD") != nullptr;
-    static const bool on = [] {
-        const char* e = getenv("LSR_FWD_SHARE");
-        return !(e && e[0] == '0');
-    }();
-    if (explicit_pad || !on || !p.shared_cu) return forward_pad();
+    if (!p.shared_cu) return 0;
     static const size_t pad[3] = {
-        occupancy_pad((const void*)k_render_forward<false, true, true>, kSharedWgsFwd, "forward (loss)"),
-        occupancy_pad((const void*)k_render_forward<false, true, false>, kSharedWgsFwd, "forward (feature)"),
-        occupancy_pad((const void*)k_render_forward<false, false, false>, kSharedWgsFwd, "forward (colour)")};
+        occupancy_pad((const void*)k_render_forward<false, true, true>, kSharedWgsFwd),
+        occupancy_pad((const void*)k_render_forward<false, true, false>, kSharedWgsFwd),
+        occupancy_pad((const void*)k_render_forward<false, false, false>, kSharedWgsFwd)};
     return pad[variant];
 }
 
@@ -1050,20 +853,15 @@ hipError_t launch_render_forward(const RenderParams& pin, int tiles, hipStream_t
 {
     if (tiles == 0) return hipSuccess;
     RenderParams p = pin;
-    if (split_color_forced()) p.split_color = 1;
-    if (!scheduled()) p.sched_counts = p.sched_lists = nullptr;
-    if (!p.sched_counts || !split_replay()) p.split_pool = nullptr;
-    p.prio = p.sched_counts ? prio_levels() : 0;
+    if (!p.sched_counts) p.split_pool = nullptr;
+    p.prio = p.sched_counts ? 1 : 0;
     const bool feat = p.include_feature != 0;
     const bool loss = feat && p.loss_words != nullptr;  // one word per workgroup: the full grid
     if (render_stats_on() && !loss) {
-        tiles = debug_grid(tiles);
         if (feat)
-            hipLaunchKernelGGL((k_render_forward<true, true, false>), dim3(tiles), dim3(kTilePixels), forward_pad(), s,
-                               p);
+            hipLaunchKernelGGL((k_render_forward<true, true, false>), dim3(tiles), dim3(kTilePixels), 0, s, p);
         else
-            hipLaunchKernelGGL((k_render_forward<true, false, false>), dim3(tiles), dim3(kTilePixels), forward_pad(), s,
-                               p);
+            hipLaunchKernelGGL((k_render_forward<true, false, false>), dim3(tiles), dim3(kTilePixels), 0, s, p);
     } else if (loss) {
         hipLaunchKernelGGL((k_render_forward<false, true, true>), dim3(tiles), dim3(kTilePixels),
                            forward_launch_pad(p, 0), s, p);
@@ -1271,17 +1069,16 @@ __device__ __forceinline__ void bwd_pixel_blend(BwdPixel& q, float G, float og, 
 // v[9..11] (language).  Reduce-scatter: lane bit 5 picks v0 / f0, v1 / f1, f2 / - (permlane32),
 // bit 4 r0 / r1 (permlane16; r2 summed on both sides), bit 3 s0 / s1 (row_mirror), then bits 2..0.
 // Lane l then holds the wave total of value scatter_index5(l); scatter_writer5 picks one lane each.
-#ifndef LSR_BWD_DPP_DROP  // measurement knob: the last n (0..2) quad DPP steps left to the LDS atomics
-#define LSR_BWD_DPP_DROP 0  // (2^n writer lanes per value, each adding a partial sum): backward 141 ->
-#endif                      // 145 (n = 1) and 224 us (n = 2), same-address ds_add_f32 serialise
+// (Leaving the last n quad DPP steps to the LDS atomics, 2^n writer lanes per value, measured worse:
+// backward 141 -> 145 (n = 1) and 224 us (n = 2), same-address ds_add_f32 serialise.)
 __device__ __forceinline__ float wave_reduce_scatter5(const float (&v)[12], int lane)
 {
     const float r0 = swap32_add(v[0], v[9]), r1 = swap32_add(v[1], v[10]), r2 = swap32_add(v[11], 0.0f);
     const float s0 = swap16_add(r0, r1), s1 = swap16_add(r2, r2);
     float w = mirror_add<0x140>(s0, s1, (lane & 8) != 0);  // row_mirror
     w += dpp<0x141>(w);                                   // row_half_mirror
-    if (LSR_BWD_DPP_DROP < 2) w += dpp<0x4E>(w);          // quad_perm [2,3,0,1]
-    if (LSR_BWD_DPP_DROP < 1) w += dpp<0xB1>(w);          // quad_perm [1,0,3,2]
+    w += dpp<0x4E>(w);                                    // quad_perm [2,3,0,1]
+    w += dpp<0xB1>(w);                                    // quad_perm [1,0,3,2]
     // keep the last add next to its DPP move (one v_add_f32_dpp) instead of letting it sink into
     // the writers' branch as a separate v_mov_dpp + v_add
     asm volatile("" : "+v"(w));
@@ -1296,8 +1093,7 @@ __device__ __forceinline__ int scatter_index5(int lane)
 
 __device__ __forceinline__ bool scatter_writer5(int lane)
 {
-    constexpr int kPart = (1 << LSR_BWD_DPP_DROP) - 1;  // lanes of a quad holding partial sums
-    return (lane & 7 & ~kPart) == 0 && (!(lane & 8) || (lane & 48) == 0);
+    return (lane & 7) == 0 && (!(lane & 8) || (lane & 48) == 0);
 }
 
 // LDS slot of gradient value c: without the colour gradient values 6..8 are not stored; in the
@@ -1354,9 +1150,6 @@ __device__ __forceinline__ BwdEntry load_entry(const float4* sA, const float4* s
     return e;
 }
 
-#ifndef LSR_BWD_F_EARLY  // 1: the language step's feature record read beside A and B (measurement knob)
-#define LSR_BWD_F_EARLY 1
-#endif
 // One entry of a wave's back-to-front walk: the exact skip tests of the forward, the blend and the
 // wave reduce-scatter of its partials into the tile sums (sG = this lane's value slot of entry 0,
 // entry j at + j kGS).  kk = the entry's list index.
@@ -1373,7 +1166,7 @@ __device__ __forceinline__ void bwd_walk_entry(BwdPixel& q, const BwdEntry& E, i
     // compiler sinks it into the blend's block, a second LDS round trip on the visit's chain): the
     // empty asm takes it as an operand here, after the power, by when it has landed with A and B
     float4 Fv = E.F;
-    if (k5 && LSR_BWD_F_EARLY) asm volatile("" : "+v"(Fv.x), "+v"(Fv.y), "+v"(Fv.z), "+v"(Fv.w));
+    if (k5) asm volatile("" : "+v"(Fv.x), "+v"(Fv.y), "+v"(Fv.z), "+v"(Fv.w));
     bool h = kk < (int)q.last && pw <= 0.0f && pw >= B.z;
     if (__ballot(h) == 0ull) return;  // wave-uniform skip
     // hardware exp (a few ulp): gradients need 1e-4.  Only the 1/255 skip decision must equal the
@@ -1426,9 +1219,6 @@ __device__ __forceinline__ void bwd_walk_entry(BwdPixel& q, const BwdEntry& E, i
     }
 }
 
-#ifndef LSR_BWD_NOFLUSH  // measurement only: 1 drops the flush atomics (wrong gradients)
-#define LSR_BWD_NOFLUSH 0
-#endif
 template <bool kStats, bool kFeat, bool kColor, bool kGeo>
 __global__ __launch_bounds__(kTilePixels) void k_render_backward(RenderParams p)
 {
@@ -1589,7 +1379,7 @@ __global__ __launch_bounds__(kTilePixels) void k_render_backward(RenderParams p)
         for (int slot = t; slot < cnt * kGS; slot += kThreads) {
             const int e = slot / kGS, cs = slot - kGS * e;
             const float v = sG[slot];
-            if (v == 0.0f || LSR_BWD_NOFLUSH) continue;
+            if (v == 0.0f) continue;
             if (k5) {  // packed 20-B record: dxy in slots 0, 1, the language feature in 2..4
                 const float val = v * (cs == 0 ? (float)p.W : cs == 1 ? (float)p.H : 1.0f);
                 const size_t g = s_gid[e];
@@ -1637,24 +1427,18 @@ hipError_t render_timeline_read(uint32_t* out, int kernel, int n)
 // LSR_BWD_SHARED_CU: the dynamic LDS that caps a backward workgroup's CU at kSharedWgs workgroups
 // (kSharedWgs x (static + pad) fits the CU's 160 KiB, one more does not), so that the pipelined
 // step's other stream finds wave slots beside it.  Measured at C3 for the language-step variant
-// (18704 B static; tools/pg_host.py with LSR_BWD_PAD, profiles/r05_occupancy_sweep.txt): 8 workgroups
+// (18704 B static; profiles/r05_occupancy_sweep.txt): 8 workgroups
 // per CU (no pad) 0.417-0.421 ms per step; 7 with 18.6 KB of LDS left over (pad 2048) 0.406; 7 with
 // 4.2 KB left (pad 4096) 0.400-0.401; 6 (pad 5120) 0.478; 5 (pad 8192) 0.416.  So the pad is the
-// largest that still fits 7.  LSR_BWD_SHARE=0 disables it (LSR_BWD_PAD then applies).
+// largest that still fits 7.
 template <int V>
 static size_t shared_pad_of()
 {
-    return occupancy_pad((const void*)k_render_backward<false, (V & 1) != 0, (V & 2) != 0, (V & 4) != 0>, kSharedWgsBwd,
-                         "backward");
+    return occupancy_pad((const void*)k_render_backward<false, (V & 1) != 0, (V & 2) != 0, (V & 4) != 0>, kSharedWgsBwd);
 }
 
 static size_t shared_cu_pad(int variant)
 {
-    static const bool on = [] {
-        const char* e = getenv("LSR_BWD_SHARE");
-        return !(e && e[0] == '0');
-    }();
-    if (!on) return backward_pad();
     // variant bits (launch_render_backward): 1 feature, 2 colour, 4 geometry
     static const size_t pad[8] = {shared_pad_of<0>(), shared_pad_of<1>(), shared_pad_of<2>(), shared_pad_of<3>(),
                                   shared_pad_of<4>(), shared_pad_of<5>(), shared_pad_of<6>(), shared_pad_of<7>()};
@@ -1665,15 +1449,13 @@ hipError_t launch_render_backward(const RenderParams& pin, int tiles, hipStream_
 {
     if (tiles == 0) return hipSuccess;
     RenderParams p = pin;
-    if (!scheduled()) p.sched_counts = p.sched_lists = nullptr;
-    p.prio = p.sched_counts ? prio_levels() : 0;
+    p.prio = p.sched_counts ? 1 : 0;
     const bool feat = p.include_feature != 0;
     const bool color = p.dL_dcolor != nullptr;  // null: the colour image does not reach the loss
     const int variant = (feat ? 1 : 0) | (color ? 2 : 0) | (p.geo ? 4 : 0);
-    if (!p.sched_counts || !split_replay()) p.split_pool = nullptr;
+    if (!p.sched_counts) p.split_pool = nullptr;
     if (p.split_pool) tiles *= kSplitItems;  // the items: up to kSplitItems chunks per tile
-    if (render_stats_on()) tiles = debug_grid(tiles);
-    const size_t pad = p.shared_cu && !render_stats_on() ? shared_cu_pad(variant) : backward_pad();
+    const size_t pad = p.shared_cu && !render_stats_on() ? shared_cu_pad(variant) : 0;
 #define LSR_BWD(S, V)                                                                                         \
     hipLaunchKernelGGL((k_render_backward<S, (V & 1) != 0, (V & 2) != 0, (V & 4) != 0>), dim3(tiles), \
                        dim3(kTilePixels), pad, s, p)

@@ -119,9 +119,6 @@ class PipelinedGraphStep:
         stream A:  wait geo[p] -> G_comp[p] -> record step[p]
         stream B:  G_geo[r] -> record geo[r]
 
-    (LSR_PG_MERGE=0 or LSR_PG_GEO=fwd: the composite and the step as two graphs, with the event
-    comp[p] between them; the geometry then may wait for it.)
-
     so a replay is one full language step (the loss it returns is that of the view it composited and
     updated from) and later views' geometry overlaps it.  Two graphs on two streams are separate
     queues: unlike one graph with two branches (which this HIP runtime launches on one queue in
@@ -161,16 +158,15 @@ class PipelinedGraphStep:
     queue each at C3) and the following R views' geometry on stream B; the replays in between launch
     nothing.  Parameters, learning rates and check() apply at rotation boundaries (k % R == 0).
 
-    Knobs (measured at C3): LSR_PG_SETS (2 or 3), LSR_PG_GEO=fwd (the geometry starts
-    only after this view's compositing), LSR_PG_PRIO=geo|step (stream priorities), LSR_PG_ROT."""
+    Knobs: the `sets` argument (default 3), LSR_PG_ROT (the `rotation` argument's default),
+    LSR_PG_DEFER=0 (N > 1: the gradient epilogue stays in the backward) and LSR_PG_NATIVE_LAUNCH=0
+    (every replay through torch's stream context).  Forms measured at C3 and not kept (DESIGN.md
+    §5b): the geometry starting only after this view's compositing, stream priorities, the composite
+    and the step as two graphs, a host throttle on the replays enqueued ahead."""
 
     def __init__(self, forward_fn, params, optimizer, headroom: float = 1.125, warmup: int = 2, bucket=None,
-                 slots=None, sets: int = None, rotation: int = None, model=None, bucket_factory=None,
-                 ahead: int = None):
+                 slots=None, sets: int = None, rotation: int = None, model=None, bucket_factory=None):
         self.forward_fn = forward_fn
-        # replay() waits on the host until step k - ahead has finished before enqueuing step k
-        # (0: no limit; LSR_PG_AHEAD)
-        self.ahead = int(ahead if ahead is not None else os.environ.get("LSR_PG_AHEAD", "0"))
         self.model = model  # its active_sh_degree is part of the capture key (graph.capture_key)
         self.params = [p for p in params]
         self.optimizer = optimizer
@@ -179,16 +175,14 @@ class PipelinedGraphStep:
         self.headroom = float(headroom)
         self.warmup = int(warmup)
         dev = self.params[0].device
-        # three sets by default: measured at C3 (tools/pg_sweep.py, one box) 0.435 ms per step against
-        # 0.482 with two; a view's geometry then runs two steps ahead, beside the backward and the
+        # three sets by default: measured at C3 (one box) 0.435 ms per step against 0.482 with two; a view's geometry then runs two steps ahead, beside the backward and the
         # next compositing, and no compositing waits on a cross-stream event that is not yet signalled
         # rotation R > 1: R consecutive steps per stream-A graph over 2 R buffer sets (N = 1 only)
         R = int(rotation if rotation is not None else os.environ.get("LSR_PG_ROT", "1"))
         if R < 1 or (R > 1 and bucket is not None):
             raise ValueError("PipelinedGraphStep: rotation >= 1, and > 1 only without a bucket (N = 1)")
         self.R = R
-        S = int(sets if sets is not None else (len(slots) if slots else
-                                               (2 * R if R > 1 else os.environ.get("LSR_PG_SETS", "3"))))
+        S = int(sets if sets is not None else (len(slots) if slots else (2 * R if R > 1 else 3)))
         if S < 2:
             raise ValueError("PipelinedGraphStep: at least two buffer sets")
         if R > 1 and S != 2 * R:
@@ -199,13 +193,10 @@ class PipelinedGraphStep:
         self.slots = list(slots) if slots is not None else None
         self.sets = tuple(_native.static_buffers() for _ in range(S))
         # A: step, B: geometry.  (Stream priorities measured worse: a high-priority geometry stream
-        # 0.82 ms per step, a high-priority step stream 0.57, none 0.48; LSR_PG_PRIO=geo / step)
-        prio = os.environ.get("LSR_PG_PRIO", "none")
-        # the later view's geometry starts with the step ("start") or after this view's compositing
-        # ("fwd": beside the backward and Adam only); measured C3 with 2 sets: start 0.49, fwd 0.54 ms
-        self.geo_after_fwd = os.environ.get("LSR_PG_GEO", "start") == "fwd"
-        self.streams = (torch.cuda.Stream(dev, priority=-1 if prio == "step" else 0),
-                        torch.cuda.Stream(dev, priority=-1 if prio == "geo" else 0))
+        # 0.82 ms per step, a high-priority step stream 0.57, none 0.48.)
+        # The later view's geometry starts with the step; starting it after this view's compositing
+        # (beside the backward and Adam only) measured C3 with 2 sets 0.54 against 0.49 ms.
+        self.streams = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
         self.overflow = tuple(torch.zeros((), dtype=torch.int32, device=dev) for _ in range(S))
         self._one = torch.ones((), device=dev)
         self._reset_graphs()
@@ -219,10 +210,10 @@ class PipelinedGraphStep:
 
     def _reset_graphs(self):
         S = self.S
-        self.g_geo, self.g_comp, self.g_step, self.g_adam = [None] * S, [None] * S, [None] * S, [None] * S
+        self.g_geo, self.g_comp, self.g_adam = [None] * S, [None] * S, [None] * S
         self.grads = [None] * S
         self.static_loss = [None] * S
-        self.ev_geo = self.ev_comp = self.ev_step = [None] * S
+        self.ev_geo = self.ev_step = [None] * S
         self.g_rot = self.g_rot0 = None
         self.k = 0
         self.primed = False
@@ -323,11 +314,8 @@ class PipelinedGraphStep:
         # filled by the step before
         self.g_comp0 = None
         self.grads0 = None
-        # the composite and the step in ONE graph per set (default): a graph boundary on stream A
-        # costs ~16-24 us of idle queue at C3 (rocprofv3 trace, round 4), and nothing needs the point
-        # between them unless the geometry waits for the compositing (LSR_PG_GEO=fwd)
-        merged = not self.geo_after_fwd and os.environ.get("LSR_PG_MERGE", "1") != "0"
-        self.merged = merged
+        # the composite and the step are ONE graph per set: a graph boundary on stream A costs ~16-24 us
+        # of idle queue at C3 (rocprofv3 trace, round 4), and nothing needs the point between them
 
         def update_ctx(p):
             if defer:  # this set's deferred tail (its arguments stay with the context)
@@ -351,16 +339,12 @@ class PipelinedGraphStep:
                 elif self.bucket is None or coll_in_graph:
                     self.optimizer.step(skip=self.overflow[p], fill=adam_fill(p))
 
-        geo_delay = int(os.environ.get("LSR_PG_GEO_DELAY_US", "0"))
-        step_delay = int(os.environ.get("LSR_PG_STEP_DELAY_US", "0"))
         for p in range(S):
             if self.R > 1:
                 continue  # geometry and steps are captured per rotation group below
             g = torch.cuda.CUDAGraph()
             with graph_capture(g, stream=sb), caps[p], self.sets[p], \
                     _native.forward_phase(_native.forward_phase.GEOMETRY):
-                if geo_delay:  # measurement knob: the geometry stream starts later in each step
-                    _native._check(_native.load().lsr_debug_delay(geo_delay, _native._stream(dev)), "delay")
                 self._fwd(p)  # its outputs are written by the composite half
             self.g_geo[p] = g
             for q in self.params:
@@ -370,30 +354,18 @@ class PipelinedGraphStep:
                 with graph_capture(g, stream=sa):
                     with caps[p], self.sets[p], _native.forward_phase(_native.forward_phase.COMPOSITE):
                         loss = self._fwd(p)
-                    if merged:
-                        step_body(p, loss)
-                if merged:
-                    self.grads0 = [q.grad for q in self.params]
-                    del loss
-                    for q in self.params:
-                        q.grad = None
-                else:
-                    del loss
+                    step_body(p, loss)
+                self.grads0 = [q.grad for q in self.params]
+                del loss
+                for q in self.params:
+                    q.grad = None
                 self.g_comp0 = g
             g = torch.cuda.CUDAGraph()
             with graph_capture(g, stream=sa):
-                if step_delay:  # measurement knob: the step stream starts each step later
-                    _native._check(_native.load().lsr_debug_delay(step_delay, _native._stream(dev)), "delay")
                 with caps[p], self.sets[p], _native.forward_phase(comp_phase):
                     loss = self._fwd(p)
-                if merged:
-                    step_body(p, loss)
+                step_body(p, loss)
             self.g_comp[p] = g
-            if not merged:
-                g = torch.cuda.CUDAGraph()
-                with graph_capture(g, stream=sa):
-                    step_body(p, loss)
-                self.g_step[p] = g
             self.grads[p] = [q.grad for q in self.params]  # this set's graph-owned gradients
             if self.bucket is not None and not coll_in_graph:  # the all-reduce sits between two graphs
                 g = torch.cuda.CUDAGraph()
@@ -411,7 +383,6 @@ class PipelinedGraphStep:
         cur.wait_stream(sb)
         self.ev_rot = [torch.cuda.Event() for _ in range(2)]
         self.ev_geo = [torch.cuda.Event() for _ in range(S)]
-        self.ev_comp = [torch.cuda.Event() for _ in range(S)]
         self.ev_step = [torch.cuda.Event() for _ in range(S)]
         self.ev_cur = [torch.cuda.Event() for _ in range(S)]
         self._since_capture = 0
@@ -530,17 +501,15 @@ class PipelinedGraphStep:
         P = int(self.params[0].shape[0])
         return geom.data_ptr() + _native.state_layout(P, int(W), int(H), 0)["record"]
 
-    def _geometry(self, r, after=None, released=None):
+    def _geometry(self, r, released=None):
         """Set r's geometry graph on stream B, after everything the caller's stream holds (the set's
         view loaded, its last reader finished) or, with `released` (an event: the set's last reader
-        done), after that alone [and after `after`]."""
+        done), after that alone."""
         sb = self.streams[1]
         if released is not None:
             sb.wait_event(released)
         else:
             sb.wait_stream(torch.cuda.current_stream())
-        if after is not None:
-            sb.wait_event(after)
         with torch.cuda.stream(sb):
             self.g_geo[r].replay()
         self.ev_geo[r].record(sb)
@@ -586,10 +555,6 @@ class PipelinedGraphStep:
         sa, sb = self.streams
         p = self.k % S
         r = (self.k + S - 1) % S
-        if 0 < self.ahead < S and self._since_capture >= self.ahead:
-            # host throttle: at most `ahead` steps enqueued beyond the running one (the queues stay
-            # short; a step's stream-A work still follows the previous step without a host gap)
-            self.ev_step[(self.k - self.ahead) % S].synchronize()
         fast = not wait and self._since_capture >= S - 1
         if wait and self._fast:  # back from fast replays: the lagged events were not recorded
             self._since_capture = 0
@@ -622,10 +587,10 @@ class PipelinedGraphStep:
             self._loaded[r] = next_view
         first = self.k == 0 and self.g_comp0 is not None
         refill = self._refill and (self.fused or self.fill_after) and not first
-        # Steady state (the merged step graph, no update graph, no refill): the stream-A waits, the
+        # Steady state (no update graph, no refill): the stream-A waits, the
         # launch and the step's event in ONE native call (lsr_graph_launch); the Python path below
         # costs ~8 us more host time before the launch, which a loss.item() loop pays every step
-        launcher = (self._launcher(p, fast) if self.merged and self.g_adam[p] is None and not first and not refill
+        launcher = (self._launcher(p, fast) if self.g_adam[p] is None and not first and not refill
                     and self._since_capture >= S - 1 else None)
         if launcher is not None:
             self._since_capture += 1
@@ -657,9 +622,6 @@ class PipelinedGraphStep:
                     self._refill_records(p)
                 self._refill = False
                 (self.g_comp0 if first else self.g_comp[p]).replay()
-                if not self.merged:
-                    self.ev_comp[p].record(sa)
-                    self.g_step[p].replay()
                 if self.g_adam[p] is not None:
                     for q, g in zip(self.params, self.grads[p]):
                         q.grad = g
@@ -671,12 +633,11 @@ class PipelinedGraphStep:
         if not fast:
             self.ev_cur[self.k % S].record(cur)
         # view k + S - 1's geometry into set r
-        after = self.ev_comp[p] if self.geo_after_fwd and not self.merged else None
         if fast:
             # the set's view (if any) was loaded on stream B itself
-            self._geometry(r, after=after, released=self.ev_step[(self.k - 1) % S])
+            self._geometry(r, released=self.ev_step[(self.k - 1) % S])
         else:
-            self._geometry(r, after=after)
+            self._geometry(r)
             cur.wait_event(self.ev_step[p])
         self.k += 1
         return self.static_loss[p]
@@ -688,7 +649,7 @@ class PipelinedGraphStep:
             raise RuntimeError("PipelinedGraphStep.last_grads: no replay yet")
         if self.R > 1 and self.k <= self.R and self.g_rot0 is not None:
             return self.g_rot0[1][self.k - 1]
-        if self.k == 1 and self.merged and self.g_comp0 is not None:
+        if self.k == 1 and self.g_comp0 is not None:
             return self.grads0
         return self.grads[(self.k - 1) % self.S]
 

@@ -136,7 +136,7 @@ def test_query_args_layout_matches_header(tmp_path):
 def test_query_entry_point_is_exported_without_an_abi_bump():
     lib = _native.load()
     assert hasattr(lib, "lsr_query_relevancy") and "lsr_query_relevancy" in _native.SIGNATURES
-    assert lib.lsr_abi_version() == 17
+    assert lib.lsr_abi_version() == 18  # 17 when the query was added; 18 removed a measurement hook
 
 
 def test_invalid_query_arguments_report_errors_without_gpu():

@@ -2,8 +2,8 @@
 
     python3 tools/c5_msd_check.py
 
-Renders the C5 forward twice, once with the LSD depth order (LSR_DEPTH_LSD=1) and once with the MSD
-bucket sort forced on (LSR_MSD_MAX_KEYS=4000000), prints each one's per-kernel times, and compares
+Renders the C5 forward twice, once with the LSD depth order (LSR_DEPTH_LSD=1) and once with the
+default (C5's 3M keys take the 512-bucket MSD sort), prints each one's per-kernel times, and compares
 the images, tile ranges, point list, final T and contributor counts for bit equality.
 """
 import os, sys, time
@@ -26,9 +26,9 @@ args = (ind["means3D"], ind["shs"], None, ind["language_feature_precomp"], ind["
 outs = {}
 for mode in ("lsd", "msd"):
     if mode == "lsd":
-        os.environ["LSR_DEPTH_LSD"] = "1"; os.environ.pop("LSR_MSD_MAX_KEYS", None)
+        os.environ["LSR_DEPTH_LSD"] = "1"
     else:
-        os.environ.pop("LSR_DEPTH_LSD", None); os.environ["LSR_MSD_MAX_KEYS"] = "4000000"
+        os.environ.pop("LSR_DEPTH_LSD", None)
     out = _native.rasterize_gaussians(std, *args, flags=_native.FWD_ZERO_GRAD_RECORDS)
     torch.cuda.synchronize()
     nr = out[0]
