@@ -537,6 +537,71 @@ typedef struct lsr_query_args {
 } lsr_query_args;
 int32_t lsr_query_relevancy(const lsr_query_args* args, void* stream);
 
+/* ---- LERF evaluation -----------------------------------------------------
+ * What activate_stream and lerf_localization (eval/evaluate_iou_loc.py:90-217) do with
+ * get_max_across's (levels, n_prompts, H, W) relevancy after their first line, for n_maps = levels *
+ * n_prompts maps of H x W floats (row-major, tightly packed), in two calls on one stream.
+ *
+ * lsr_eval_filter (:107-112, :176-187): per map
+ *     avg   = cv2.filter2D(map, -1, ones((30, 30)) / 900) with cv2's defaults: a correlation, the
+ *             anchor at ksize / 2 = 15, so the taps are offsets -15 .. +14 in both axes; border
+ *             BORDER_REFLECT_101 (gfedcb|abcdefgh|gfedcba, the edge sample not repeated), reflected
+ *             with period 2 (n - 1) as often as needed, so any H, W >= 2 works.  Separable: 30 taps
+ *             along x, then 30 along y, each as three chains of 10 consecutive taps added in a fixed
+ *             order, the sum divided by 900 once (no sliding window);
+ *     blend = 0.5f * (avg + map);
+ *     stats = min(blend), max(blend), max(avg) and the FIRST row-major index at which avg has that
+ *             maximum (np.argmax / the first row of np.nonzero(avg == max)).
+ * out_avg and out_blend may each be NULL (not written); stats are always written.  While the call's
+ * kernels run, a record holds order-preserving integer keys (integer atomic min / max, the arg-max as
+ * a 64-bit max over key << 32 | ~index); the call's last kernel turns them into the fields below.
+ * stats must be 8-byte aligned.  Maps are expected to be free of NaNs; -0 orders below +0.
+ *
+ * lsr_eval_masks (:129-143, eval/utils.py:46-55), after lsr_eval_filter on the same stream: per map
+ *     raw mask: o = x - mn; o = o / ((mx - mn) + 1e-9f); o = o * 2.0f + (-1.0f); o = clamp(o, 0, 1);
+ *               m = o > thresh   (mn, mx = the map's stats.blend_min / blend_max; the division is
+ *               the correctly rounded one; a constant map divides by 1e-9f and gives an empty mask);
+ *     smoothed mask: smooth() with its quirks: pixel (i, j) looks at rows max(0, i-3) ..
+ *               min(i+4, H-1) - 1 and the same range of columns -- the upper bound is exclusive and
+ *               clipped to H-1, not H, so the last row and the last column are never inside a window
+ *               -- and becomes 1 exactly when 2 * ones > window size (a tie gives 0);
+ *     with gt_mask (n_prompts x H x W bytes, non-zero = set; map m uses prompt m % n_prompts, the
+ *               (levels, n_prompts, H, W) layout): out_counts[2 m] = |gt AND smoothed|,
+ *               out_counts[2 m + 1] = |gt OR smoothed| (integer atomic adds).
+ * out_mask_raw may be NULL.  Without gt_mask, n_prompts and out_counts are not read.
+ *
+ * All arithmetic is fp32 without contraction; no float atomics; two calls, on any streams, give
+ * bit-identical results.  Both calls return LSR_ERR_INVALID before any device work for null args or
+ * a null required pointer, H < 2, W < 2, H * W >= 2^31, n_maps < 0, and (with gt_mask) n_prompts < 1
+ * or n_maps % n_prompts != 0.  n_maps == 0 is valid and enqueues nothing.  Neither call waits for
+ * the device.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect them by symbol. */
+typedef struct lsr_eval_stats {
+    float blend_min, blend_max;   /* of blend */
+    float avg_max;                /* of avg */
+    int32_t avg_argmax;           /* first row-major index (y * W + x) with avg == avg_max */
+} lsr_eval_stats;
+typedef struct lsr_eval_filter_args {
+    int32_t n_maps, H, W;
+    const float* maps;            /* device: n_maps x H x W */
+    float* out_avg;               /* NULL, or device n_maps x H x W */
+    float* out_blend;             /* NULL, or device n_maps x H x W */
+    lsr_eval_stats* out_stats;    /* device: n_maps records */
+} lsr_eval_filter_args;
+int32_t lsr_eval_filter(const lsr_eval_filter_args* args, void* stream);
+typedef struct lsr_eval_mask_args {
+    int32_t n_maps, H, W;
+    const float* blend;           /* device: n_maps x H x W (lsr_eval_filter's out_blend) */
+    const lsr_eval_stats* stats;  /* device: n_maps records (lsr_eval_filter's out_stats) */
+    float thresh;
+    int32_t n_prompts;            /* with gt_mask: the number of ground-truth masks */
+    const uint8_t* gt_mask;       /* NULL, or device n_prompts x H x W */
+    uint8_t* out_mask;            /* device: n_maps x H x W, the smoothed masks (0 / 1) */
+    uint8_t* out_mask_raw;        /* NULL, or device n_maps x H x W, the masks before smoothing */
+    int64_t* out_counts;          /* with gt_mask: device n_maps x 2 (intersection, union) */
+} lsr_eval_mask_args;
+int32_t lsr_eval_masks(const lsr_eval_mask_args* args, void* stream);
+
 size_t lsr_masked_l1_scratch_bytes(int32_t C, int64_t HW);
 int32_t lsr_masked_l1_forward(int32_t C, int64_t HW, const float* pred, const float* gt, const void* mask,
                               int32_t mask_is_float, float* loss, void* scratch, void* stream);

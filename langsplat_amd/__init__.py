@@ -4,8 +4,10 @@ The hot path (forward + backward of RasterizeGaussians, BASELINE.json north_star
 implemented as HIP kernels for gfx950 in csrc/, exposed through the C ABI of include/lsr.h
 (liblsr.so) and wrapped here with the reference's Python API.
 """
+from .lerf_eval import activate_stream, evaluate_frame, lerf_localization, smooth_relevancy  # noqa: F401
 from .query import Decoder, decode, relevancy_map, render_relevancy  # noqa: F401
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
-           "Decoder", "decode", "relevancy_map", "render_relevancy"]
+           "Decoder", "decode", "relevancy_map", "render_relevancy",
+           "smooth_relevancy", "activate_stream", "lerf_localization", "evaluate_frame"]

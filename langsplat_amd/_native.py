@@ -96,6 +96,22 @@ class LsrQueryArgs(ctypes.Structure):
                 ("n_neg", ctypes.c_int32), ("phrases", _vp), ("out_relevancy", _vp), ("out_decoded", _vp)]
 
 
+class LsrEvalStats(ctypes.Structure):
+    _fields_ = [("blend_min", ctypes.c_float), ("blend_max", ctypes.c_float), ("avg_max", ctypes.c_float),
+                ("avg_argmax", ctypes.c_int32)]
+
+
+class LsrEvalFilterArgs(ctypes.Structure):
+    _fields_ = [("n_maps", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("maps", _vp),
+                ("out_avg", _vp), ("out_blend", _vp), ("out_stats", _vp)]
+
+
+class LsrEvalMaskArgs(ctypes.Structure):
+    _fields_ = [("n_maps", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("blend", _vp),
+                ("stats", _vp), ("thresh", ctypes.c_float), ("n_prompts", ctypes.c_int32), ("gt_mask", _vp),
+                ("out_mask", _vp), ("out_mask_raw", _vp), ("out_counts", _vp)]
+
+
 ALLOC_FN = ctypes.CFUNCTYPE(_vp, _vp, ctypes.c_int32, ctypes.c_size_t)
 
 # symbol -> (restype, argtypes); must cover every function declared in include/lsr.h
@@ -114,6 +130,8 @@ SIGNATURES = {
                                       _vp]),
     "lsr_mark_visible": (ctypes.c_int32, [ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "lsr_query_relevancy": (ctypes.c_int32, [ctypes.POINTER(LsrQueryArgs), _vp]),
+    "lsr_eval_filter": (ctypes.c_int32, [ctypes.POINTER(LsrEvalFilterArgs), _vp]),
+    "lsr_eval_masks": (ctypes.c_int32, [ctypes.POINTER(LsrEvalMaskArgs), _vp]),
     "lsr_fill_language": (ctypes.c_int32, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_adam_step": (ctypes.c_int32, [ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_int64, _vp]),

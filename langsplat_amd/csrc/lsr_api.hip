@@ -950,6 +950,50 @@ int32_t lsr_query_relevancy(const lsr_query_args* a, void* stream_ptr)
     return LSR_OK;
 }
 
+// the checks lsr_eval_filter and lsr_eval_masks share; null when the shape is valid
+static const char* eval_shape_error(int32_t n_maps, int32_t H, int32_t W)
+{
+    if (n_maps < 0) return "invalid n_maps";
+    if (H < 2 || W < 2) return "invalid size (H and W are at least 2)";
+    if ((int64_t)H * (int64_t)W >= ((int64_t)1 << 31)) return "invalid size (H * W must be below 2^31)";
+    return nullptr;
+}
+
+int32_t lsr_eval_filter(const lsr_eval_filter_args* a, void* stream_ptr)
+{
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_eval_filter: null args");
+    if (const char* why = eval_shape_error(a->n_maps, a->H, a->W)) {
+        char buf[128];
+        snprintf(buf, sizeof(buf), "lsr_eval_filter: %s", why);
+        return fail(LSR_ERR_INVALID, buf);
+    }
+    if (!a->maps || !a->out_stats) return fail(LSR_ERR_INVALID, "lsr_eval_filter: null pointer");
+    if ((reinterpret_cast<uintptr_t>(a->out_stats) & 7) != 0)
+        return fail(LSR_ERR_INVALID, "lsr_eval_filter: out_stats must be 8-byte aligned");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    LSR_TRY(launch_eval_filter(*a, stream), "eval filter");
+    return LSR_OK;
+}
+
+int32_t lsr_eval_masks(const lsr_eval_mask_args* a, void* stream_ptr)
+{
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_eval_masks: null args");
+    if (const char* why = eval_shape_error(a->n_maps, a->H, a->W)) {
+        char buf[128];
+        snprintf(buf, sizeof(buf), "lsr_eval_masks: %s", why);
+        return fail(LSR_ERR_INVALID, buf);
+    }
+    if (!a->blend || !a->stats || !a->out_mask || (a->gt_mask && !a->out_counts))
+        return fail(LSR_ERR_INVALID, "lsr_eval_masks: null pointer");
+    if (a->gt_mask && (a->n_prompts < 1 || a->n_maps % a->n_prompts != 0))
+        return fail(LSR_ERR_INVALID, "lsr_eval_masks: invalid n_prompts (at least 1, and a divisor of n_maps)");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    LSR_TRY(launch_eval_masks(*a, stream), "eval masks");
+    return LSR_OK;
+}
+
 int32_t lsr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
                          uint8_t* visible, void* stream_ptr)
 {

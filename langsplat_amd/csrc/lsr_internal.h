@@ -474,6 +474,10 @@ struct QueryParams {
 };
 hipError_t launch_query(QueryParams& p, hipStream_t s);
 
+// lsr_eval_filter / lsr_eval_masks (lsr_eval.hip): the validated public argument structs as they are
+hipError_t launch_eval_filter(const lsr_eval_filter_args& a, hipStream_t s);
+hipError_t launch_eval_masks(const lsr_eval_mask_args& a, hipStream_t s);
+
 hipError_t launch_render_forward(const RenderParams& p, int tiles, hipStream_t s);
 hipError_t launch_render_backward(const RenderParams& p, int tiles, hipStream_t s);
 // the fused loss of an empty scene (P == 0: no render forward runs) into p.out_loss
