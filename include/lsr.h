@@ -602,6 +602,61 @@ typedef struct lsr_eval_mask_args {
 } lsr_eval_mask_args;
 int32_t lsr_eval_masks(const lsr_eval_mask_args* args, void* stream);
 
+/* ---- the RGB stage's loss (train.py:100-103 with include_feature=False) ------------------------
+ *     Ll1  = l1_loss(image, gt_image)                                    utils/loss_utils.py:17-18
+ *     loss = (1 - lambda_dssim) * Ll1 + lambda_dssim * (1 - ssim(image, gt_image))      :23-63
+ * for `planes` = B * C independent image planes of H x W floats (row-major, tightly packed).
+ * ssim is the reference's with size_average=True: per plane the window g g^T, g the 11-tap Gaussian
+ * with sigma 1.5 (normalised in fp64, then rounded to fp32), zero padding of 5 and no renormalisation at the
+ * borders, C1 = 0.01^2, C2 = 0.03^2, the mean of the map over all planes and pixels.  The window is
+ * applied separably (rows, then columns): the same sums in another rounding order.
+ *
+ * lsr_rgb_loss_forward writes out_terms = {loss, l1, ssim}.  With out_maps it also writes, for the
+ * backward, three H x W maps per plane (map m of plane p at out_maps[(m * planes + p) * H * W]): the
+ * partial derivatives of the pixel's SSIM value S by its windowed means mu1 = E[x], E[x^2] and E[xy],
+ * the latter two taken as variables of their own.  out_maps NULL: no gradient is wanted and nothing
+ * is written.  out_ssim_map (optional) receives S per pixel.  `scratch` holds
+ * lsr_rgb_loss_scratch_bytes(planes, H, W) bytes, 8-byte aligned; it needs no initialisation and one
+ * scratch serves any sequence of calls on one stream.  The two sums are reduced in a fixed order
+ * (per-workgroup partials in double, then one block): two calls give bit-identical terms.
+ *
+ * lsr_rgb_loss_backward writes
+ *     dL/dimage = dL_dloss * [ (1 - lambda) / N * sign(x - y)
+ *                              - lambda / N * (conv(Ma) + 2 x conv(Mb) + y conv(Mc)) ]
+ * with N = planes * H * W, sign(0) = 0 (torch's abs backward), conv the same zero-padded window (it
+ * is symmetric, so it is its own adjoint) and Ma, Mb, Mc the forward's maps; dL_dloss is a device
+ * scalar.  There is no gradient for the target.
+ *
+ * Both return LSR_ERR_INVALID before any device work for null args, a null required pointer,
+ * planes / H / W < 1, more than 2^31 - 1 tiles, or a scratch that is not 8-byte aligned.  Neither
+ * waits for the device; no float atomics.  LSR_RGB_LOSS_TILE_H x LSR_RGB_LOSS_TILE_W is the tile of
+ * one workgroup (tests place their sizes around it).
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect them by symbol. */
+#define LSR_RGB_LOSS_TILE_H 32
+#define LSR_RGB_LOSS_TILE_W 32
+typedef struct lsr_rgb_loss_args {
+    int32_t planes, H, W;
+    float lambda_dssim;
+    const float* image;           /* device: planes x H x W */
+    const float* target;          /* device: planes x H x W */
+    float* out_terms;             /* device: 3 floats {loss, l1, ssim} */
+    float* out_maps;              /* NULL, or device 3 x planes x H x W */
+    float* out_ssim_map;          /* NULL, or device planes x H x W */
+    void* scratch;                /* device: lsr_rgb_loss_scratch_bytes(planes, H, W) bytes */
+} lsr_rgb_loss_args;
+typedef struct lsr_rgb_loss_bwd_args {
+    int32_t planes, H, W;
+    float lambda_dssim;
+    const float* image;           /* device: planes x H x W */
+    const float* target;          /* device: planes x H x W */
+    const float* maps;            /* device: 3 x planes x H x W (the forward's out_maps) */
+    const float* dL_dloss;        /* device scalar */
+    float* out_dL_dimage;         /* device: planes x H x W */
+} lsr_rgb_loss_bwd_args;
+size_t lsr_rgb_loss_scratch_bytes(int32_t planes, int32_t H, int32_t W);
+int32_t lsr_rgb_loss_forward(const lsr_rgb_loss_args* args, void* stream);
+int32_t lsr_rgb_loss_backward(const lsr_rgb_loss_bwd_args* args, void* stream);
+
 size_t lsr_masked_l1_scratch_bytes(int32_t C, int64_t HW);
 int32_t lsr_masked_l1_forward(int32_t C, int64_t HW, const float* pred, const float* gt, const void* mask,
                               int32_t mask_is_float, float* loss, void* scratch, void* stream);

@@ -5,9 +5,11 @@ implemented as HIP kernels for gfx950 in csrc/, exposed through the C ABI of inc
 (liblsr.so) and wrapped here with the reference's Python API.
 """
 from .lerf_eval import activate_stream, evaluate_frame, lerf_localization, smooth_relevancy  # noqa: F401
+from .loss import rgb_loss, ssim  # noqa: F401
 from .query import Decoder, decode, relevancy_map, render_relevancy  # noqa: F401
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",
            "Decoder", "decode", "relevancy_map", "render_relevancy",
-           "smooth_relevancy", "activate_stream", "lerf_localization", "evaluate_frame"]
+           "smooth_relevancy", "activate_stream", "lerf_localization", "evaluate_frame",
+           "rgb_loss", "ssim"]

@@ -112,6 +112,21 @@ class LsrEvalMaskArgs(ctypes.Structure):
                 ("out_mask", _vp), ("out_mask_raw", _vp), ("out_counts", _vp)]
 
 
+RGB_LOSS_TILE = (32, 32)  # include/lsr.h LSR_RGB_LOSS_TILE_H, LSR_RGB_LOSS_TILE_W
+
+
+class LsrRgbLossArgs(ctypes.Structure):
+    _fields_ = [("planes", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("lambda_dssim", ctypes.c_float), ("image", _vp), ("target", _vp), ("out_terms", _vp),
+                ("out_maps", _vp), ("out_ssim_map", _vp), ("scratch", _vp)]
+
+
+class LsrRgbLossBwdArgs(ctypes.Structure):
+    _fields_ = [("planes", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("lambda_dssim", ctypes.c_float), ("image", _vp), ("target", _vp), ("maps", _vp),
+                ("dL_dloss", _vp), ("out_dL_dimage", _vp)]
+
+
 ALLOC_FN = ctypes.CFUNCTYPE(_vp, _vp, ctypes.c_int32, ctypes.c_size_t)
 
 # symbol -> (restype, argtypes); must cover every function declared in include/lsr.h
@@ -132,6 +147,9 @@ SIGNATURES = {
     "lsr_query_relevancy": (ctypes.c_int32, [ctypes.POINTER(LsrQueryArgs), _vp]),
     "lsr_eval_filter": (ctypes.c_int32, [ctypes.POINTER(LsrEvalFilterArgs), _vp]),
     "lsr_eval_masks": (ctypes.c_int32, [ctypes.POINTER(LsrEvalMaskArgs), _vp]),
+    "lsr_rgb_loss_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "lsr_rgb_loss_forward": (ctypes.c_int32, [ctypes.POINTER(LsrRgbLossArgs), _vp]),
+    "lsr_rgb_loss_backward": (ctypes.c_int32, [ctypes.POINTER(LsrRgbLossBwdArgs), _vp]),
     "lsr_fill_language": (ctypes.c_int32, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_adam_step": (ctypes.c_int32, [ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_int64, _vp]),

@@ -1018,6 +1018,54 @@ int32_t lsr_fill_language(int32_t P, const float* language_feature, int32_t raw,
     return LSR_OK;
 }
 
+// planes / H / W >= 1 and a grid that fits: nullptr, or what is wrong
+static const char* rgb_loss_shape_error(int32_t planes, int32_t H, int32_t W)
+{
+    if (planes < 1 || H < 1 || W < 1) return "invalid size (planes, H and W are at least 1)";
+    if (rgb_loss_blocks(planes, H, W) > (int64_t)INT32_MAX) return "invalid size (more than 2^31 - 1 tiles)";
+    return nullptr;
+}
+
+size_t lsr_rgb_loss_scratch_bytes(int32_t planes, int32_t H, int32_t W)
+{
+    if (planes < 1 || H < 1 || W < 1) return 0;
+    return rgb_loss_scratch_bytes(planes, H, W);
+}
+
+int32_t lsr_rgb_loss_forward(const lsr_rgb_loss_args* a, void* stream_ptr)
+{
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_rgb_loss_forward: null args");
+    if (const char* why = rgb_loss_shape_error(a->planes, a->H, a->W)) {
+        char buf[128];
+        snprintf(buf, sizeof(buf), "lsr_rgb_loss_forward: %s", why);
+        return fail(LSR_ERR_INVALID, buf);
+    }
+    if (!a->image || !a->target || !a->out_terms || !a->scratch)
+        return fail(LSR_ERR_INVALID, "lsr_rgb_loss_forward: null pointer");
+    if ((reinterpret_cast<uintptr_t>(a->scratch) & 7) != 0)
+        return fail(LSR_ERR_INVALID, "lsr_rgb_loss_forward: scratch must be 8-byte aligned");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    LSR_TRY(launch_rgb_loss_forward(*a, stream), "rgb loss");
+    return LSR_OK;
+}
+
+int32_t lsr_rgb_loss_backward(const lsr_rgb_loss_bwd_args* a, void* stream_ptr)
+{
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_rgb_loss_backward: null args");
+    if (const char* why = rgb_loss_shape_error(a->planes, a->H, a->W)) {
+        char buf[128];
+        snprintf(buf, sizeof(buf), "lsr_rgb_loss_backward: %s", why);
+        return fail(LSR_ERR_INVALID, buf);
+    }
+    if (!a->image || !a->target || !a->maps || !a->dL_dloss || !a->out_dL_dimage)
+        return fail(LSR_ERR_INVALID, "lsr_rgb_loss_backward: null pointer");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    LSR_TRY(launch_rgb_loss_backward(*a, stream), "rgb loss backward");
+    return LSR_OK;
+}
+
 size_t lsr_masked_l1_scratch_bytes(int32_t C, int64_t HW)
 {
     (void)C;

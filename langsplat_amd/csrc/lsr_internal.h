@@ -452,6 +452,14 @@ hipError_t launch_decode_language_feature(int H, int W, const int64_t* seg_level
                                           const float* feature_map, float* out, uint8_t* mask, uint32_t* bad,
                                           hipStream_t s);
 
+// lsr_rgb_loss_* (lsr_rgbloss.hip): the validated public argument structs as they are; a workgroup
+// owns one kRgbTileH x kRgbTileW tile of one plane and leaves two double partial sums in scratch
+constexpr int kRgbTileH = LSR_RGB_LOSS_TILE_H, kRgbTileW = LSR_RGB_LOSS_TILE_W;
+int64_t rgb_loss_blocks(int planes, int H, int W);
+size_t rgb_loss_scratch_bytes(int planes, int H, int W);
+hipError_t launch_rgb_loss_forward(const lsr_rgb_loss_args& a, hipStream_t s);
+hipError_t launch_rgb_loss_backward(const lsr_rgb_loss_bwd_args& a, hipStream_t s);
+
 // lsr_query_relevancy (lsr_query.hip): the decoder MLP, normalisation, phrase similarities and
 // relevancy of kQPix pixels per workgroup
 constexpr int kQPix = 64;

@@ -14,6 +14,11 @@ copies to the GPU every step; the loss is ~11 torch kernels forward + backward. 
 
 `masked_l1_loss(pred, gt, mask)` equals `l1_loss(pred * mask, gt * mask)` (same value up to
 summation order; the gradient is bit-identical to torch autograd's).  All work runs in liblsr.so.
+
+The RGB stage's loss (train.py:100-103, include_feature=False) is `rgb_loss(image, gt_image,
+opt.lambda_dssim)`: (1 - lambda) * L1 + lambda * (1 - SSIM) with utils/loss_utils.py:23-63's SSIM, one
+kernel and a one-block reduction forward, one kernel backward; `ssim(a, b)` is the
+value alone.
 """
 from __future__ import annotations
 
@@ -98,6 +103,101 @@ def masked_l1_loss(pred: torch.Tensor, gt: torch.Tensor, mask: torch.Tensor) -> 
     """l1_loss(pred * mask, gt * mask) of train.py:98 as one HIP kernel (backward: one more).
     pred, gt: (C,H,W) fp32 on the GPU; mask: (1,H,W) or (H,W), bool or float, broadcast over C."""
     return _MaskedL1.apply(pred, gt, mask)
+
+
+_RGB_SCRATCH: Dict[Tuple[int, int], torch.Tensor] = {}
+
+
+def _rgb_scratch(device: torch.device, planes: int, H: int, W: int) -> torch.Tensor:
+    """Per (device, stream) partial-sum scratch of the RGB loss, grown to the largest image seen;
+    the kernels overwrite what they read, so it needs no initialisation."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream(device).cuda_stream)
+    nbytes = int(_native.load().lsr_rgb_loss_scratch_bytes(planes, H, W))
+    t = _RGB_SCRATCH.get(key)
+    if t is None or t.numel() < nbytes:
+        t = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        _RGB_SCRATCH[key] = t
+    return t
+
+
+def _rgb_planes(image: torch.Tensor, gt: torch.Tensor, what: str, differentiable: bool = True):
+    if image.device.type != "cuda" or gt.device.type != "cuda":
+        raise RuntimeError(f"{what}: tensors must be on a ROCm GPU device; there is no CPU path")
+    if image.dim() not in (3, 4) or image.shape != gt.shape or image.numel() == 0:
+        raise ValueError(f"{what}: image and gt must both be (C,H,W) or (B,C,H,W) and not empty; got "
+                         f"{tuple(image.shape)} and {tuple(gt.shape)}")
+    if differentiable and gt.requires_grad:
+        raise ValueError(f"{what}: gt requires grad, but no gradient is produced for the target")
+    H, W = int(image.shape[-2]), int(image.shape[-1])
+    return image.numel() // (H * W), H, W
+
+
+def _rgb_forward(x, y, planes, H, W, lambda_dssim, want_maps, want_ssim_map=False):
+    """lsr_rgb_loss_forward on torch's current stream: (terms (3,), maps or None, ssim map or None)."""
+    dev = x.device
+    terms = torch.empty((3,), dtype=torch.float32, device=dev)
+    maps = torch.empty((3, planes, H, W), dtype=torch.float32, device=dev) if want_maps else None
+    smap = torch.empty((planes, H, W), dtype=torch.float32, device=dev) if want_ssim_map else None
+    a = _native.LsrRgbLossArgs(planes, H, W, float(lambda_dssim), x.data_ptr(), y.data_ptr(), terms.data_ptr(),
+                               maps.data_ptr() if want_maps else None, smap.data_ptr() if want_ssim_map else None,
+                               _rgb_scratch(dev, planes, H, W).data_ptr())
+    with _native._on_device(dev):
+        _native._check(_native.load().lsr_rgb_loss_forward(ctypes.byref(a), _stream_ptr(dev)), "lsr_rgb_loss_forward")
+    return terms, maps, smap
+
+
+class _RgbLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, gt, lambda_dssim, want):
+        planes, H, W = _rgb_planes(image, gt, "rgb_loss")
+        x = image.detach().to(torch.float32).contiguous()
+        y = gt.detach().to(torch.float32).contiguous()
+        terms, maps, _ = _rgb_forward(x, y, planes, H, W, lambda_dssim, want)
+        if want:
+            ctx.save_for_backward(x, y, maps)
+        ctx.lambda_dssim = float(lambda_dssim)
+        ctx.in_dtype = image.dtype
+        ctx.mark_non_differentiable(terms)
+        return terms[0], terms
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_terms):
+        x, y, maps = ctx.saved_tensors
+        _, planes, H, W = maps.shape
+        gl = grad_loss.detach().to(torch.float32).contiguous()
+        out = torch.empty_like(x)
+        a = _native.LsrRgbLossBwdArgs(planes, H, W, ctx.lambda_dssim, x.data_ptr(), y.data_ptr(), maps.data_ptr(),
+                                      gl.data_ptr(), out.data_ptr())
+        with _native._on_device(x.device):
+            _native._check(_native.load().lsr_rgb_loss_backward(ctypes.byref(a), _stream_ptr(x.device)),
+                           "lsr_rgb_loss_backward")
+        return out.to(ctx.in_dtype), None, None, None
+
+
+def rgb_loss(image: torch.Tensor, gt: torch.Tensor, lambda_dssim: float = 0.2, return_terms: bool = False):
+    """The RGB stage's loss of train.py:100-103,
+        (1 - lambda_dssim) * l1_loss(image, gt) + lambda_dssim * (1 - ssim(image, gt)),
+    as one HIP kernel and a one-block reduction (backward: one more kernel); include/lsr.h
+    lsr_rgb_loss_forward.  image, gt: (C,H,W) or (B,C,H,W) on the GPU, every plane on its own as in
+    utils/loss_utils.py:35-63.  Returns the scalar loss, or with return_terms (loss, l1, ssim), the last
+    two detached.  The gradient goes to `image` only; a gt that requires grad is refused.  When image
+    needs no gradient (or under torch.no_grad()) the maps for the backward are not allocated."""
+    # forward() runs with grad mode off and ctx.needs_input_grad ignores torch.no_grad(): decided here
+    want = torch.is_grad_enabled() and image.requires_grad
+    loss, terms = _RgbLoss.apply(image, gt, lambda_dssim, want)
+    if return_terms:
+        return loss, terms[1], terms[2]
+    return loss
+
+
+def ssim(img1: torch.Tensor, img2: torch.Tensor) -> torch.Tensor:
+    """utils/loss_utils.py:35-63's ssim(img1, img2) (window 11, size_average=True), the value alone (no
+    gradient): lsr_rgb_loss_forward with lambda = 1."""
+    planes, H, W = _rgb_planes(img1, img2, "ssim", differentiable=False)
+    x = img1.detach().to(torch.float32).contiguous()
+    y = img2.detach().to(torch.float32).contiguous()
+    return _rgb_forward(x, y, planes, H, W, 1.0, False)[0][2]
 
 
 def decode_language_feature(seg_map: torch.Tensor, feature_map: torch.Tensor, feature_level: int):
