@@ -139,8 +139,7 @@ CASES = [
 def test_forward_bit_exact_and_backward(case):
     st, inp = scene(scale_range=(0.03, 0.2), **case)
     run, std, ind, out = check_forward_exact(st, inp)
-    if case.get("scale_modifier", 1.0) == 1.0:
-        check_backward(st, inp, run, out)
+    check_backward(st, inp, run, out)
 
 
 @pytest.mark.parametrize("seed", [0, 5])
