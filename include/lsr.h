@@ -57,7 +57,8 @@ enum lsr_buffer {
     LSR_BUF_GEOM = 0,     /* per Gaussian; forward -> backward */
     LSR_BUF_BINNING = 1,  /* per tile instance; forward -> backward */
     LSR_BUF_IMAGE = 2,    /* per pixel / per tile; forward -> backward */
-    LSR_BUF_BACKWARD = 3  /* per Gaussian gradient scratch, backward only */
+    LSR_BUF_BACKWARD = 3, /* per Gaussian gradient scratch, backward only */
+    LSR_BUF_LEVELS = 4    /* per Gaussian: the extra levels' activated features, lsr_forward_levels only */
 };
 
 /* Returns device memory of at least `bytes` bytes, 256-byte aligned, valid until the caller
@@ -656,6 +657,52 @@ typedef struct lsr_rgb_loss_bwd_args {
 size_t lsr_rgb_loss_scratch_bytes(int32_t planes, int32_t H, int32_t W);
 int32_t lsr_rgb_loss_forward(const lsr_rgb_loss_args* args, void* stream);
 int32_t lsr_rgb_loss_backward(const lsr_rgb_loss_bwd_args* args, void* stream);
+
+/* ---- all language levels of a scene in one rasterizer pass (inference) ---------------------------
+ * LangSplat trains its semantic levels from ONE RGB checkpoint with the geometry frozen
+ * (scene/gaussian_model.py:203-217 with include_feature; train.py:222 writes <model>_1/_2/_3), so
+ * the level models share means, SH, opacity, scales and rotations bit for bit and differ only in
+ * their P x 3 language feature -- and evaluation wants the levels together
+ * (eval/evaluate_iou_loc.py:258-266 stacks the rendered maps).  lsr_forward_levels renders up to
+ * LSR_MAX_LEVELS of them with one geometry pass and one compositing walk that carries 3 * levels
+ * language channels.
+ *
+ * Contract.  The call is inference only (no backward state is written; lsr_backward must not follow).
+ * The preprocess, depth order, binning, colour image, radii, `visible` and *num_rendered are those of
+ * lsr_forward with the same `fwd`.  Level 0 is fwd.language_feature -> fwd.out_language_feature;
+ * level l >= 1 is more_language_feature[(l - 1) P 3 ...] -> more_out_language_feature[(l - 1) 3 H W ...].
+ * Level l's map is bit-identical to the out_language_feature of an lsr_forward whose language_feature
+ * is level l's tensor: each channel is its own fma(f, w, acc) chain in list order, with the blend
+ * weight w = alpha T shared by all channels.  There is no background term: empty tiles, P == 0 and
+ * fully culled scenes give zeros in every level.  levels == 1 behaves exactly as lsr_forward.
+ * fwd.raw & LSR_RAW_LANGUAGE applies to every level (all raw or all activated).
+ *
+ * The extra levels' activated features of the visible Gaussians are staged in one scratch array,
+ * requested as LSR_BUF_LEVELS (P > 0 and levels > 1 only): ceil(3 (levels - 1) / 4) float4 per
+ * Gaussian, {l1.0 l1.1 l1.2 l2.0}{l2.1 l2.2 l3.0 l3.1}{l3.2 - - -}, so a list entry's gather is whole
+ * 16-byte loads.  lsr_levels_bytes is exactly that request (0 for levels == 1 or P <= 0).
+ *
+ * Refused with LSR_ERR_INVALID before any device work, the message naming the field: levels outside
+ * 1..LSR_MAX_LEVELS; reserved != 0; settings.include_feature == 0; fwd.flags != LSR_FWD_NO_BACKWARD;
+ * loss_target, loss_mask or out_loss set; language_ready set; phase != LSR_PHASE_ALL;
+ * capacity_rendered != 0 (no graph capture of this form); with P > 0 a NULL fwd.language_feature;
+ * with levels > 1 a NULL more_out_language_feature or (P > 0) more_language_feature.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+#define LSR_MAX_LEVELS 4            /* feature_level 0..3, scene/cameras.py:75-88 */
+typedef struct lsr_forward_levels_args {
+    lsr_forward_args fwd;                  /* as lsr_forward; language_feature / out_language_feature are level 0 */
+    int32_t levels;                        /* 1 .. LSR_MAX_LEVELS */
+    int32_t reserved;                      /* 0 */
+    const float* more_language_feature;    /* (levels-1) x P x 3; raw iff fwd.raw & LSR_RAW_LANGUAGE; NULL iff levels == 1 */
+    float* more_out_language_feature;      /* (levels-1) x 3 x H x W */
+} lsr_forward_levels_args;
+size_t lsr_levels_bytes(int32_t P, int32_t levels);
+int32_t lsr_forward_levels(const lsr_settings* settings, const lsr_forward_levels_args* args, lsr_alloc_fn alloc,
+                           void* alloc_user, void* stream, int64_t* num_rendered);
+/* Measurement hook, not part of the reference interface: the workgroups per CU the HIP runtime grants
+ * the inference compositing kernel of `levels` levels (1: lsr_forward's) on the current device, from
+ * its registers and LDS with the hardware's allocation granules; negative (-lsr_status) on error. */
+int32_t lsr_debug_levels_occupancy(int32_t levels);
 
 size_t lsr_masked_l1_scratch_bytes(int32_t C, int64_t HW);
 int32_t lsr_masked_l1_forward(int32_t C, int64_t HW, const float* pred, const float* gt, const void* mask,

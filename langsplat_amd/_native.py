@@ -21,7 +21,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # LSR_LIB: a measurement variant built by tools/build_variant.py (same-box A/B); default the product
 LIB_PATH = os.environ.get("LSR_LIB") or os.path.join(_HERE, "liblsr.so")
 
-LSR_BUF_GEOM, LSR_BUF_BINNING, LSR_BUF_IMAGE, LSR_BUF_BACKWARD = 0, 1, 2, 3
+LSR_BUF_GEOM, LSR_BUF_BINNING, LSR_BUF_IMAGE, LSR_BUF_BACKWARD, LSR_BUF_LEVELS = 0, 1, 2, 3, 4
+MAX_LEVELS = 4  # include/lsr.h LSR_MAX_LEVELS
 ABI_VERSION = 18
 ADAM_STEP_WORDS = 66  # include/lsr.h LSR_ADAM_STEP_WORDS
 ADAM_WORD_SKIPPED, ADAM_WORD_LR = 49, 50  # LSR_ADAM_WORD_SKIPPED / LSR_ADAM_WORD_LR
@@ -59,6 +60,11 @@ class LsrForwardArgs(ctypes.Structure):
          ("loss_target", _vp), ("loss_mask", _vp), ("out_loss", _vp), ("capacity_rendered", ctypes.c_int64),
          ("capacity_entries", ctypes.c_int64), ("overflow", _vp), ("out_num_entries", ctypes.POINTER(ctypes.c_int64)),
          ("language_ready", _vp), ("phase", ctypes.c_int32)]
+
+
+class LsrForwardLevelsArgs(ctypes.Structure):
+    _fields_ = [("fwd", LsrForwardArgs), ("levels", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("more_language_feature", _vp), ("more_out_language_feature", _vp)]
 
 
 class LsrAdamTensor(ctypes.Structure):
@@ -143,6 +149,10 @@ SIGNATURES = {
                                      _vp, ctypes.POINTER(ctypes.c_int64)]),
     "lsr_backward": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrBackwardArgs), ALLOC_FN, _vp,
                                       _vp]),
+    "lsr_levels_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
+    "lsr_debug_levels_occupancy": (ctypes.c_int32, [ctypes.c_int32]),
+    "lsr_forward_levels": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrForwardLevelsArgs),
+                                            ALLOC_FN, _vp, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "lsr_mark_visible": (ctypes.c_int32, [ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "lsr_query_relevancy": (ctypes.c_int32, [ctypes.POINTER(LsrQueryArgs), _vp]),
     "lsr_eval_filter": (ctypes.c_int32, [ctypes.POINTER(LsrEvalFilterArgs), _vp]),
@@ -665,6 +675,64 @@ def rasterize_gaussians(rs, means3D, shs, colors_precomp, language_feature, opac
         LAST_COUNTS[(P, W, H)] = (int(nr.value), int(entries.value))
     return (int(nr.value), color, lang, radii, alloc.get(LSR_BUF_GEOM), alloc.get(LSR_BUF_BINNING),
             alloc.get(LSR_BUF_IMAGE))
+
+
+def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_features, opacities, scales, rotations,
+                               cov3D_precomp, raw=0, shs_rest=None, with_visibility=False):
+    """All language levels of a scene in one inference forward (include/lsr.h lsr_forward_levels):
+    language_features is (L, P, 3), 1 <= L <= MAX_LEVELS, raw iff raw has RAW_LANGUAGE; the other
+    arguments are rasterize_gaussians'.  Returns (num_rendered, color (3, H, W), language_images
+    (L, 3, H, W), radii), and with_visibility the (P,) bool radii > 0 after them.  Level l's image is
+    bit-identical to rasterize_gaussians' for language_features[l]; nothing is kept for a backward."""
+    lib = load()
+    device = means3D.device
+    P = int(means3D.shape[0])
+    if language_features is None or language_features.dim() != 3 or tuple(language_features.shape[1:]) != (P, 3) \
+            or not 1 <= int(language_features.shape[0]) <= MAX_LEVELS:
+        got = None if language_features is None else tuple(language_features.shape)
+        raise ValueError(f"rasterize_gaussians_levels: language_features must have shape (L, P, 3) with "
+                         f"1 <= L <= {MAX_LEVELS} and P = {P}, got {got}")
+    L = int(language_features.shape[0])
+    H, W = int(rs.image_height), int(rs.image_width)
+    keep: list = []
+    s = make_settings(rs, keep)
+    lf = _f32c(language_features.detach())
+    color = torch.empty((3, H, W), dtype=torch.float32, device=device)
+    langs = torch.empty((L, 3, H, W), dtype=torch.float32, device=device)
+    radii = torch.empty((P,), dtype=torch.int32, device=device)  # preprocess writes every entry
+    visible = torch.empty((P,), dtype=torch.bool, device=device) if with_visibility else None
+    la = LsrForwardLevelsArgs()
+    a = la.fwd
+    a.P = P
+    a.M = int(shs.shape[1]) if shs is not None and shs.numel() > 0 else 0
+    if shs_rest is not None and shs_rest.numel() > 0:
+        a.M += int(shs_rest.shape[1])
+        a.shs_rest = _ptr(shs_rest)
+    a.raw = int(raw)
+    a.flags = FWD_NO_BACKWARD
+    a.means3D = _ptr(means3D)
+    a.shs = _ptr(shs)
+    a.colors_precomp = _ptr(colors_precomp)
+    a.language_feature = _ptr(lf)
+    a.opacities = _ptr(opacities)
+    a.scales = _ptr(scales)
+    a.rotations = _ptr(rotations)
+    a.cov3D_precomp = _ptr(cov3D_precomp)
+    a.out_color = _ptr(color)
+    a.out_language_feature = _ptr(langs)
+    a.radii = _ptr(radii)
+    a.visible = _ptr(visible)
+    la.levels = L
+    if L > 1:
+        la.more_language_feature = _ptr(lf[1:])
+        la.more_out_language_feature = _ptr(langs[1:])
+    alloc = _Allocator(device)
+    nr = ctypes.c_int64(0)
+    with _on_device(device), alloc:
+        _check(lib.lsr_forward_levels(ctypes.byref(s), ctypes.byref(la), _ALLOC_CB, None, _stream(device),
+                                      ctypes.byref(nr)), "lsr_forward_levels")
+    out = (int(nr.value), color, langs, radii)
+    return out + (visible,) if with_visibility else out
 
 
 # LSR_ALL_GRADS=1 (or setting this to True) computes every geometry gradient even when no input

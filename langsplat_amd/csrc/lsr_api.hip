@@ -256,9 +256,19 @@ static AdamScalars adam_scalars(double lr, double beta1, double beta2, double ep
     return a;
 }
 
-// The render forward of lsr_forward (both modes), after the binning.
+// lsr_forward_levels' additions to a forward: the extra levels' inputs and outputs, and the level
+// array (LSR_BUF_LEVELS) once it is allocated
+struct LevelsCall {
+    int levels;  // 2 .. LSR_MAX_LEVELS
+    const float* more;
+    float* out_more;
+    float4* lev;
+};
+
+// The render forward of lsr_forward (both modes), after the binning.  lv: lsr_forward_levels' form.
 static int32_t render_forward_and_finish(const lsr_settings* s, const lsr_forward_args* a, const Layout& L, char* geom,
-                                         char* image, char* binning, HostBlock* hb, hipStream_t stream, bool debug)
+                                         char* image, char* binning, HostBlock* hb, hipStream_t stream, bool debug,
+                                         const LevelsCall* lv = nullptr)
 {
     const int P = a->P, W = s->image_width, H = s->image_height;
     (void)P;
@@ -301,9 +311,23 @@ static int32_t render_forward_and_finish(const lsr_settings* s, const lsr_forwar
         rp.spin_limit = stall_spin_limit();
         rp.stall = &hb->stall;
     }
+    if (lv) {
+        RenderLevelsParams lp{};
+        lp.r = rp;
+        lp.lev = lv->lev;
+        lp.out_more = lv->out_more;
+        lp.levels = lv->levels;
+        LSR_TRY(launch_render_forward_levels(lp, L.tiles, stream), "render forward");
+        return LSR_OK;
+    }
     LSR_TRY(launch_render_forward(rp, L.tiles, stream), "render forward");
     return LSR_OK;
 }
+
+// lsr_forward, and with lv lsr_forward_levels (validated there: inference, one phase, no capacity
+// mode, no fused loss, no deferred feature).
+static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
+                            void* stream_ptr, int64_t* num_rendered, LevelsCall* lv);
 
 extern "C" {
 
@@ -359,6 +383,14 @@ static hipError_t wait_and_fill_language(const lsr_forward_args* a, const Layout
 int32_t lsr_forward(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
                     void* stream_ptr, int64_t* num_rendered)
 {
+    return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, nullptr);
+}
+
+}  // extern "C"
+
+static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
+                            void* stream_ptr, int64_t* num_rendered, LevelsCall* lv)
+{
     if (!s || !a || !alloc || !num_rendered) return fail(LSR_ERR_INVALID, "lsr_forward: null argument");
     const int P = a->P, W = s->image_width, H = s->image_height;
     if (P < 0 || W <= 0 || H <= 0 || W > 65535 * kTile || H > 65535 * kTile)
@@ -399,6 +431,7 @@ int32_t lsr_forward(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_
         // upstream leaves the images at their zero initialisation when there is nothing to draw
         LSR_TRY(zero_fill(a->out_color, 3 * HW * 4, stream), "memset color");
         LSR_TRY(zero_fill(a->out_language_feature, 3 * HW * 4, stream), "memset language");
+        if (lv) LSR_TRY(zero_fill(lv->out_more, (size_t)(lv->levels - 1) * 3 * HW * 4, stream), "memset language");
         if (a->out_loss) {
             const Layout L0 = make_layout(0, W, H, 0, 0);
             char* image = static_cast<char*>(alloc(user, LSR_BUF_IMAGE, L0.image_bytes));
@@ -426,6 +459,10 @@ int32_t lsr_forward(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_
     char* geom = static_cast<char*>(alloc(user, LSR_BUF_GEOM, L.geom_bytes));
     char* image = static_cast<char*>(alloc(user, LSR_BUF_IMAGE, L.image_bytes));
     if (!geom || !image) return fail(LSR_ERR_ALLOC, "lsr_forward: geometry/image buffer allocation failed");
+    if (lv) {
+        lv->lev = static_cast<float4*>(alloc(user, LSR_BUF_LEVELS, lsr_levels_bytes(P, lv->levels)));
+        if (!lv->lev) return fail(LSR_ERR_ALLOC, "lsr_forward_levels: level buffer allocation failed");
+    }
     // no memset: k_publish_counters initialises every counter word before anything reads it
     uint32_t* counters = reinterpret_cast<uint32_t*>(image + L.counters);
 
@@ -544,6 +581,9 @@ int32_t lsr_forward(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_
     const bool fused_emit = !depth_order_uses_pass_count(P);
     LSR_TRY(launch_depth_order(P, guess, L, geom, counters, &hb->stall, stream, debug, fused_emit, 0, placed),
             "depth order");
+    // the extra levels' features of the visible Gaussians (radii are the preprocess's): enqueued here,
+    // so it runs while the host waits for the counts
+    if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
     hm.mark();
     // the binning buffer from the last forward's size while the GPU works (the allocator callback
     // is host work that would otherwise sit between the wait and the binning launches)
@@ -596,9 +636,54 @@ int32_t lsr_forward(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_
             "binning");
     if (deferred) LSR_TRY(wait_and_fill_language(a, L, geom, stream), "fill language");
     hm.mark();
-    const int32_t rc = render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug);
+    const int32_t rc = render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
     hm.mark();
     return rc;
+}
+
+extern "C" {
+
+int32_t lsr_debug_levels_occupancy(int32_t levels)
+{
+    if (levels < 1 || levels > LSR_MAX_LEVELS)
+        return -fail(LSR_ERR_INVALID, "lsr_debug_levels_occupancy: levels must be 1..LSR_MAX_LEVELS (4)");
+    const int n = render_forward_occupancy(levels);
+    return n >= 0 ? n : -fail(LSR_ERR_HIP, "lsr_debug_levels_occupancy: occupancy query failed");
+}
+
+size_t lsr_levels_bytes(int32_t P, int32_t levels)
+{
+    if (P <= 0 || levels < 2 || levels > LSR_MAX_LEVELS) return 0;
+    return align_up(sizeof(float4) * (size_t)level_quads(levels) * (size_t)P);
+}
+
+int32_t lsr_forward_levels(const lsr_settings* s, const lsr_forward_levels_args* la, lsr_alloc_fn alloc, void* user,
+                           void* stream_ptr, int64_t* num_rendered)
+{
+    if (!s || !la || !alloc || !num_rendered) return fail(LSR_ERR_INVALID, "lsr_forward_levels: null argument");
+    const lsr_forward_args* a = &la->fwd;
+    if (la->levels < 1 || la->levels > LSR_MAX_LEVELS)
+        return fail(LSR_ERR_INVALID, "lsr_forward_levels: levels must be 1..LSR_MAX_LEVELS (4)");
+    if (la->reserved != 0) return fail(LSR_ERR_INVALID, "lsr_forward_levels: reserved must be 0");
+    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_forward_levels: needs settings.include_feature");
+    if (a->flags != LSR_FWD_NO_BACKWARD)
+        return fail(LSR_ERR_INVALID, "lsr_forward_levels: inference only, fwd.flags must be LSR_FWD_NO_BACKWARD");
+    if (a->loss_target) return fail(LSR_ERR_INVALID, "lsr_forward_levels: no fused loss, fwd.loss_target must be NULL");
+    if (a->loss_mask) return fail(LSR_ERR_INVALID, "lsr_forward_levels: no fused loss, fwd.loss_mask must be NULL");
+    if (a->out_loss) return fail(LSR_ERR_INVALID, "lsr_forward_levels: no fused loss, fwd.out_loss must be NULL");
+    if (a->language_ready) return fail(LSR_ERR_INVALID, "lsr_forward_levels: fwd.language_ready must be NULL");
+    if (a->phase != LSR_PHASE_ALL) return fail(LSR_ERR_INVALID, "lsr_forward_levels: fwd.phase must be LSR_PHASE_ALL");
+    if (a->capacity_rendered != 0)
+        return fail(LSR_ERR_INVALID, "lsr_forward_levels: no capacity mode, fwd.capacity_rendered must be 0");
+    if (a->P > 0 && !a->language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_forward_levels: fwd.language_feature (level 0) is NULL");
+    if (la->levels > 1 && a->P > 0 && !la->more_language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_forward_levels: more_language_feature is NULL with levels > 1");
+    if (la->levels > 1 && !la->more_out_language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_forward_levels: more_out_language_feature is NULL with levels > 1");
+    if (la->levels == 1) return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, nullptr);
+    LevelsCall lv{la->levels, la->more_language_feature, la->more_out_language_feature, nullptr};
+    return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, &lv);
 }
 
 int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_alloc_fn alloc, void* user,

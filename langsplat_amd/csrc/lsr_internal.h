@@ -487,6 +487,24 @@ hipError_t launch_eval_filter(const lsr_eval_filter_args& a, hipStream_t s);
 hipError_t launch_eval_masks(const lsr_eval_mask_args& a, hipStream_t s);
 
 hipError_t launch_render_forward(const RenderParams& p, int tiles, hipStream_t s);
+// lsr_forward_levels: the inference forward carrying 3 * levels language channels.  r is the
+// RenderParams of the single-level inference forward (no_bwd set; level 0 in the records and in
+// r.out_lang); the extra levels' activated features come from `lev`, level_quads(levels) float4 per
+// Gaussian holding the 3 (levels - 1) floats in level-major order (zero padded), and their maps go
+// to out_more, (levels - 1) x 3 x H x W.
+struct RenderLevelsParams {
+    RenderParams r;
+    const float4* lev;
+    float* out_more;
+    int levels;  // 2 .. LSR_MAX_LEVELS
+};
+constexpr int level_quads(int levels) { return (3 * (levels - 1) + 3) / 4; }
+hipError_t launch_render_forward_levels(const RenderLevelsParams& p, int tiles, hipStream_t s);
+int render_forward_occupancy(int levels);  // lsr_debug_levels_occupancy
+// the level array of the visible Gaussians (radii > 0) from `more`, (levels - 1) x P x 3 (activated
+// here when raw has LSR_RAW_LANGUAGE, as the preprocess activates level 0)
+hipError_t launch_fill_levels(int P, int levels, const float* more, int raw, const int32_t* radii, float4* lev,
+                              hipStream_t s);
 hipError_t launch_render_backward(const RenderParams& p, int tiles, hipStream_t s);
 // the fused loss of an empty scene (P == 0: no render forward runs) into p.out_loss
 hipError_t launch_loss_background(const RenderParams& p, hipStream_t s);

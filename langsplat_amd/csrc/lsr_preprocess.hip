@@ -455,6 +455,85 @@ hipError_t launch_fill_language(int P, const float* lang, int raw, const int32_t
     return hipGetLastError();
 }
 
+// lsr_forward_levels: the extra levels' features of the visible Gaussians into the level array the
+// compositing gathers from -- level_quads(kLevels) float4 per Gaussian holding the 3 (kLevels - 1)
+// floats in level-major order, zero padded -- activated by the function the records' level 0 goes
+// through (act_lang), so every level's values are those lsr_forward would put into its records.
+// As k_fill_language: four Gaussians per thread, their 16 radius bytes and each level's 48 feature
+// bytes as whole dwordx4 loads where the run is whole and the level's tensor 16-B aligned (level l
+// starts 12 P l bytes after the first, so with P % 4 != 0 some levels take the scalar path), a scalar
+// tail otherwise.  Culled Gaussians get no store: no tile list names them.
+template <int kLevels>
+__global__ __launch_bounds__(256) void k_fill_levels(int P, const float* __restrict__ more, int raw,
+                                                     const int32_t* __restrict__ radii, float4* __restrict__ lev)
+{
+    constexpr int kE = 3 * (kLevels - 1), kQ = level_quads(kLevels);
+    const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;  // Gaussians 4 q .. 4 q + 3
+    const int64_t i0 = 4 * q;
+    if (i0 >= P) return;
+    const bool whole = i0 + 3 < P;
+    int r[4] = {0, 0, 0, 0};
+    if (whole && (reinterpret_cast<uintptr_t>(radii) & 15) == 0) {
+        const int4 r4 = reinterpret_cast<const int4*>(radii)[q];
+        r[0] = r4.x, r[1] = r4.y, r[2] = r4.z, r[3] = r4.w;
+    } else {
+        for (int k = 0; k < 4; k++)
+            if (i0 + k < P) r[k] = radii[i0 + k];
+    }
+    if (r[0] <= 0 && r[1] <= 0 && r[2] <= 0 && r[3] <= 0) return;
+    float f[4][4 * kQ];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+#pragma unroll
+        for (int e = 0; e < 4 * kQ; e++) f[k][e] = 0.0f;
+#pragma unroll
+    for (int l = 0; l < kLevels - 1; l++) {
+        const float* src = more + (size_t)l * 3 * (size_t)P;
+        float v[12];
+        if (whole && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+            const float4* l4 = reinterpret_cast<const float4*>(src) + 3 * q;
+            const float4 a = l4[0], b = l4[1], c = l4[2];
+            v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y;
+            v[6] = b.z, v[7] = b.w, v[8] = c.x, v[9] = c.y, v[10] = c.z, v[11] = c.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const bool live = r[k] > 0;  // (r[k] is 0 past P)
+#pragma unroll
+                for (int c = 0; c < 3; c++) v[3 * k + c] = live ? src[3 * (i0 + k) + c] : 0.0f;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            float3 a = make_float3(v[3 * k], v[3 * k + 1], v[3 * k + 2]);
+            if (raw & LSR_RAW_LANGUAGE) a = act_lang(a.x, a.y, a.z);
+            f[k][3 * l] = a.x;
+            f[k][3 * l + 1] = a.y;
+            f[k][3 * l + 2] = a.z;
+        }
+    }
+    static_assert(kE <= 4 * kQ, "the level floats fit their quads");
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        if (r[k] <= 0) continue;
+        float4* o = lev + (size_t)kQ * (size_t)(i0 + k);
+#pragma unroll
+        for (int j = 0; j < kQ; j++) o[j] = make_float4(f[k][4 * j], f[k][4 * j + 1], f[k][4 * j + 2], f[k][4 * j + 3]);
+    }
+}
+
+hipError_t launch_fill_levels(int P, int levels, const float* more, int raw, const int32_t* radii, float4* lev,
+                              hipStream_t s)
+{
+    if (P == 0 || levels < 2) return hipSuccess;
+    const int64_t threads = ((int64_t)P + 3) / 4;
+    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    if (levels == 2) hipLaunchKernelGGL(k_fill_levels<2>, grid, block, 0, s, P, more, raw, radii, lev);
+    else if (levels == 3) hipLaunchKernelGGL(k_fill_levels<3>, grid, block, 0, s, P, more, raw, radii, lev);
+    else hipLaunchKernelGGL(k_fill_levels<4>, grid, block, 0, s, P, more, raw, radii, lev);
+    return hipGetLastError();
+}
+
 // dynamic LDS beyond the 64 KiB default (M > 20 stored SH coefficients) must be opted into
 static hipError_t allow_lds(const void* fn, size_t bytes)
 {

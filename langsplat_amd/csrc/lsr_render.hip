@@ -876,6 +876,246 @@ hipError_t launch_render_forward(const RenderParams& pin, int tiles, hipStream_t
 }
 
 // ------------------------------------------------------------------------------------------
+// multi-level inference forward (lsr_forward_levels)
+// ------------------------------------------------------------------------------------------
+// k_render_forward's walk -- the same tile ownership and schedule, 256-entry batches, cover masks,
+// compacted lists, paired exps and alpha / stop tests, so the same blend weights w = alpha T in the
+// same order -- carrying kE = 3 (kLevels - 1) more feature sums per pixel.  Each is its own
+// fma(f, w, acc) chain (packed in pairs: the same IEEE operation per element), so every level's map
+// is the single-level forward's for that level's features.  Inference only: no cover bytes, split
+// states, work lists, final_T or n_contrib.
+//
+// Extra features e = 3 (level - 1) + channel of a batch slot: e0, e1 in the two spare floats of the
+// slot's sF record, e2..e5 in sX0, e6..e8 in sX1 (kLevels == 4 only; at kLevels == 2 one float per
+// slot of sX0 would do: the float4 keeps one addressing scheme).  Static LDS 23104 B at 2 and 3
+// levels, 27200 B at 4; the runtime grants 7, 7 and 6 workgroups per CU.
+template <int kLevels>
+struct LevelSums {
+    static constexpr int kE = 3 * (kLevels - 1);
+    static constexpr int kPairs = kE / 2;  // (e0, e1), (e2, e3), ...; an odd last one alone
+    lsr_f2 p[kPairs];
+    float s;
+};
+
+// fwd_pixel_blend<true>'s operations on the colour and level-0 sums, plus the extra levels' (Ff.z,
+// Ff.w = e0, e1; X0 = e2..e5; X1 = e6..e8)
+template <int kLevels>
+__device__ __forceinline__ void levels_pixel_blend(FwdPixel& q, LevelSums<kLevels>& x, float al, bool ok,
+                                                   const float4& Cc, const float4& Ff, const float4& X0,
+                                                   const float4& X1)
+{
+    const float a = ok ? al : 0.0f;
+    const float test_T = q.T * (1.0f - a);
+    const bool go = !(test_T < 0.0001f);
+    const float w = go ? a * q.T : 0.0f;
+    const lsr_f2 w2 = make_f2(w, w);
+    q.C01 = __builtin_elementwise_fma(make_f2(Cc.x, Cc.y), w2, q.C01);
+    q.C2F0 = __builtin_elementwise_fma(make_f2(Cc.z, Cc.w), w2, q.C2F0);
+    q.F12 = __builtin_elementwise_fma(make_f2(Ff.x, Ff.y), w2, q.F12);
+    x.p[0] = __builtin_elementwise_fma(make_f2(Ff.z, Ff.w), w2, x.p[0]);
+    if (kLevels == 2) x.s = fma_(X0.x, w, x.s);
+    if (kLevels >= 3) {
+        x.p[1] = __builtin_elementwise_fma(make_f2(X0.x, X0.y), w2, x.p[1]);
+        x.p[2] = __builtin_elementwise_fma(make_f2(X0.z, X0.w), w2, x.p[2]);
+    }
+    if (kLevels == 4) {
+        x.p[3] = __builtin_elementwise_fma(make_f2(X1.x, X1.y), w2, x.p[3]);
+        x.s = fma_(X1.z, w, x.s);
+    }
+    q.T = go ? test_T : -fabsf(q.T);
+}
+
+// render_empty_tiles for this form: background colour and zeros in every level
+__device__ void render_empty_tiles_levels(const RenderLevelsParams& lp, int j, int M)
+{
+    const RenderParams& p = lp.r;
+    const int T = p.gx * p.gy;
+    const size_t HW = (size_t)p.W * p.H;
+    for (int u = j; u < T; u += M) {
+        const uint2 r = p.ranges[u];
+        if (r.x != r.y) continue;
+        int px, py;
+        pixel_map(u % p.gx, u / p.gx, (int)threadIdx.x, px, py);
+        if (!(px < p.W && py < p.H)) continue;
+        const size_t pix = (size_t)py * p.W + px;
+        p.out_color[pix] = fma_(1.0f, p.bg[0], 0.0f);
+        p.out_color[HW + pix] = fma_(1.0f, p.bg[1], 0.0f);
+        p.out_color[2 * HW + pix] = fma_(1.0f, p.bg[2], 0.0f);
+        for (int c = 0; c < 3; c++) p.out_lang[c * HW + pix] = 0.0f;
+        for (int e = 0; e < 3 * (lp.levels - 1); e++) lp.out_more[e * HW + pix] = 0.0f;
+    }
+}
+
+// Waves per SIMD the kernel is compiled for: the single-level forward's 7 (<= 72 VGPRs) up to three
+// levels; the 9 extra sums and two more staged float4s of four levels take it past 72 (it would
+// spill in the walk), and its LDS allows 6 workgroups per CU anyway.
+template <int kLevels>
+constexpr int kLevelsWaves = kLevels <= 3 ? kFwdWaves : 6;
+template <int kLevels>
+__global__ __launch_bounds__(kTilePixels, kLevelsWaves<kLevels>) void k_render_forward_levels(RenderLevelsParams lp)
+{
+    static_assert(kLevels >= 2 && kLevels <= LSR_MAX_LEVELS, "levels 2 .. LSR_MAX_LEVELS (1: k_render_forward)");
+    constexpr int kThreads = kTilePixels;
+    constexpr int kE = 3 * (kLevels - 1), kQ = level_quads(kLevels);
+    const RenderParams& p = lp.r;
+    __shared__ float4 sA[kThreads];  // x, y, -0.5 conic.x, -0.5 conic.z
+    __shared__ float4 sB[kThreads];  // conic.y, opacity, power cutoff, -
+    __shared__ float4 sC[kThreads];  // r, g, b, f0
+    __shared__ float4 sF[kThreads];  // f1, f2, e0, e1
+    __shared__ float4 sX0[kThreads];                     // e2, e3, e4, e5
+    __shared__ float4 sX1[kLevels == 4 ? kThreads : 1];  // e6, e7, e8, -
+    __shared__ uint8_t sM[kThreads];  // entry_cover mask
+    // per-wave culled slot lists as in k_render_forward (byte offsets 16 s, four zero slots past the end)
+    __shared__ __attribute__((aligned(8))) uint16_t sL[kThreads / 64][kThreads + 8];
+
+    const int T = p.gx * p.gy;
+    int tile = (int)blockIdx.x;
+    if (p.sched_counts) {
+        tile = scheduled_tile((int)blockIdx.x, p.sched_counts + kCntFwdClass, p.sched_lists, T);
+        if (tile < 0) {  // past the tiles with entries: fill the empty ones, strided
+            const int listed = -1 - tile;
+            render_empty_tiles_levels(lp, (int)blockIdx.x - listed, T - listed);
+            return;
+        }
+    }
+    launch_priority((int)blockIdx.x, p.prio);
+    const int tx = tile % p.gx, ty = tile / p.gx;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    int px, py;
+    pixel_map(tx, ty, t, px, py);
+    const float pfx = (float)px, pfy = (float)py;
+    const lsr_f2 pxy = make_f2(pfx, pfy);
+    const float tx0 = (float)(tx * kTile), ty0 = (float)(ty * kTile);
+    const uint2 range = p.ranges[tile];
+    const uint32_t start = range.x, end = range.y;
+    const bool inside = px < p.W && py < p.H;
+
+    FwdPixel q{inside ? 1.0f : -1.0f, make_f2(0.f, 0.f), make_f2(0.f, 0.f), make_f2(0.f, 0.f), 0u, 0u};
+    LevelSums<kLevels> x;
+#pragma unroll
+    for (int k = 0; k < LevelSums<kLevels>::kPairs; k++) x.p[k] = make_f2(0.f, 0.f);
+    x.s = 0.0f;
+    // a batch's point_list ids are loaded during the previous batch's walk (k_render_forward)
+    uint32_t g_next = start + t < end ? p.point_list[start + t] : 0u;
+    for (uint32_t base = start; base < end; base += kThreads) {
+        if (__syncthreads_count(q.T < 0.0f) == kThreads) break;
+        const uint32_t idx = base + t;
+        if (idx < end) {
+            const uint32_t g = g_next;
+            const float4 a = p.record[3 * (size_t)g];
+            const float4 b = p.record[3 * (size_t)g + 1];
+            const float4 c = p.record[3 * (size_t)g + 2];
+            const float4* lv = lp.lev + (size_t)kQ * g;
+            const float4 l0 = lv[0];
+            const float4 l1 = kQ > 1 ? lv[1] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 l2 = kQ > 2 ? lv[2] : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float cut = power_cutoff(b.y);
+            sA[t] = make_float4(a.x, a.y, -0.5f * a.z, -0.5f * b.x);
+            sB[t] = make_float4(a.w, b.y, cut, 0.0f);
+            sC[t] = make_float4(b.z, b.w, c.x, c.y);
+            sF[t] = make_float4(c.z, c.w, l0.x, l0.y);
+            sX0[t] = make_float4(l0.z, l0.w, l1.x, l1.y);
+            if (kLevels == 4) sX1[t] = make_float4(l1.z, l1.w, l2.x, 0.0f);
+            sM[t] = (uint8_t)entry_cover(a.x, a.y, a.z, a.w, b.x, cut, tx0, ty0);
+        }
+        __syncthreads();
+        const int cnt = (int)min((uint32_t)kThreads, end - base);
+        const int n = __builtin_amdgcn_readfirstlane(wave_compact(sM, cnt, 1u << wave, lane, sL[wave]));
+        if (lane < 4) sL[wave][n + lane] = 0;
+        __syncthreads();  // list visible to the wave's other lanes
+        if (idx + kThreads < end) g_next = p.point_list[idx + kThreads];
+        const char* const cA = reinterpret_cast<const char*>(sA);
+        const char* const cB = reinterpret_cast<const char*>(sB);
+        const char* const cC = reinterpret_cast<const char*>(sC);
+        const char* const cF = reinterpret_cast<const char*>(sF);
+        const char* const cX0 = reinterpret_cast<const char*>(sX0);
+        const char* const cX1 = reinterpret_cast<const char*>(sX1);
+        // k_render_forward's pair_alpha: the same operations on the same records
+        auto pair_alpha = [&](uint32_t oa, uint32_t ob, bool hb, float& ala, float& alb, bool& oka, bool& okb) {
+            const float4 Aa = *reinterpret_cast<const float4*>(cA + oa), Ba = *reinterpret_cast<const float4*>(cB + oa);
+            const float4 Ab = *reinterpret_cast<const float4*>(cA + ob), Bb = *reinterpret_cast<const float4*>(cB + ob);
+            const lsr_f2 da = make_f2(Aa.x, Aa.y) - pxy, db = make_f2(Ab.x, Ab.y) - pxy;
+            const lsr_f2 ma = make_f2(Aa.z, Aa.w) * da, mb = make_f2(Ab.z, Ab.w) * db;
+            const float pwa = fma_(da.x, fma_(-Ba.x, da.y, ma.x), ma.y * da.y);
+            const float pwb = fma_(db.x, fma_(-Bb.x, db.y, mb.x), mb.y * db.y);
+            const lsr_f2 G2 = expf_exact_render2(make_f2(pwa, pwb));
+            ala = fminf(0.99f, Ba.y * G2.x);
+            alb = fminf(0.99f, Bb.y * G2.y);
+            oka = !(pwa > 0.0f || pwa < Ba.z) && !(ala < 1.0f / 255.0f);
+            okb = hb && !(pwb > 0.0f || pwb < Bb.z) && !(alb < 1.0f / 255.0f);
+        };
+        auto blend_at = [&](float al, bool ok, uint32_t o) {
+            const float4 Cc = *reinterpret_cast<const float4*>(cC + o);
+            const float4 Ff = *reinterpret_cast<const float4*>(cF + o);
+            const float4 X0 = kLevels == 2 ? make_float4(*reinterpret_cast<const float*>(cX0 + o), 0.f, 0.f, 0.f)
+                                           : *reinterpret_cast<const float4*>(cX0 + o);
+            const float4 X1 = kLevels == 4 ? *reinterpret_cast<const float4*>(cX1 + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+            levels_pixel_blend<kLevels>(q, x, al, ok, Cc, Ff, X0, X1);
+        };
+        int i = 0;
+        const uint32_t* const sL2 = reinterpret_cast<const uint32_t*>(sL[wave]);
+        uint32_t oo = sL2[0];
+        if (n > 0 && __ballot(q.T > 0.0f) != 0ull) do {
+            const uint32_t o0 = oo & 0xFFFFu, o1 = oo >> 16;
+            oo = sL2[(i >> 1) + 1];  // slots i + 2, i + 3 (<= n + 1)
+            float al0, al1;
+            bool ok0, ok1;
+            pair_alpha(o0, o1, i + 1 < n, al0, al1, ok0, ok1);
+            blend_at(al0, ok0, o0);
+            blend_at(al1, ok1, o1);
+            asm volatile("" : "+v"(oo));  // (k_render_forward: the next offsets' read stays in this step)
+            i += 2;
+        } while (i < n && __ballot(q.T > 0.0f) != 0ull);
+    }
+    if (!inside) return;
+    const size_t HW = (size_t)p.W * p.H;
+    const size_t pix = (size_t)py * p.W + px;
+    const float Tf = fabsf(q.T);
+    p.out_color[pix] = fma_(Tf, p.bg[0], q.C01.x);
+    p.out_color[HW + pix] = fma_(Tf, p.bg[1], q.C01.y);
+    p.out_color[2 * HW + pix] = fma_(Tf, p.bg[2], q.C2F0.x);
+    p.out_lang[pix] = q.C2F0.y;
+    p.out_lang[HW + pix] = q.F12.x;
+    p.out_lang[2 * HW + pix] = q.F12.y;
+    float* const om = lp.out_more + pix;  // extra e at om[e HW]
+#pragma unroll
+    for (int k = 0; k < LevelSums<kLevels>::kPairs; k++) {
+        om[(size_t)(2 * k) * HW] = x.p[k].x;
+        om[(size_t)(2 * k + 1) * HW] = x.p[k].y;
+    }
+    if (kE & 1) om[(size_t)(kE - 1) * HW] = x.s;
+}
+
+hipError_t launch_render_forward_levels(const RenderLevelsParams& pin, int tiles, hipStream_t s)
+{
+    if (tiles == 0) return hipSuccess;
+    RenderLevelsParams lp = pin;
+    lp.r.split_pool = nullptr;
+    lp.r.no_bwd = 1;
+    lp.r.prio = lp.r.sched_counts ? 1 : 0;
+    const dim3 grid(tiles), block(kTilePixels);
+    if (lp.levels == 2) hipLaunchKernelGGL(k_render_forward_levels<2>, grid, block, 0, s, lp);
+    else if (lp.levels == 3) hipLaunchKernelGGL(k_render_forward_levels<3>, grid, block, 0, s, lp);
+    else if (lp.levels == 4) hipLaunchKernelGGL(k_render_forward_levels<4>, grid, block, 0, s, lp);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// Workgroups per CU the runtime grants the inference forward of `levels` levels (1: k_render_forward)
+// on the current device -- registers and LDS with the hardware's allocation granules -- or -1.
+int render_forward_occupancy(int levels)
+{
+    const void* fn = levels == 1   ? (const void*)k_render_forward<false, true, false>
+                     : levels == 2 ? (const void*)k_render_forward_levels<2>
+                     : levels == 3 ? (const void*)k_render_forward_levels<3>
+                     : levels == 4 ? (const void*)k_render_forward_levels<4>
+                                   : nullptr;
+    int n = 0;
+    if (!fn || hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kTilePixels, 0) != hipSuccess) return -1;
+    return n;
+}
+
+// ------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------
 

@@ -169,3 +169,16 @@ def render_relevancy(viewpoint_camera, pc, pipe, bg_color, opt, decoder: Decoder
         pkg = render(viewpoint_camera, pc, pipe, bg_color, opt, scaling_modifier=scaling_modifier)
         pkg["relevancy"] = relevancy_map(pkg["language_feature_image"], decoder, pos_embeds, neg_embeds)
     return pkg
+
+
+def render_levels_relevancy(viewpoint_camera, pc, pipe, bg_color, opt, language_features, decoder: Decoder,
+                            pos_embeds, neg_embeds, scaling_modifier=1.0):
+    """levels.render_levels (every level's map from one rasterizer pass) followed by relevancy_map on
+    them: the render_levels package plus "relevancy", (L, n_pos, H, W) -- what
+    eval/evaluate_iou_loc.py:258-266 computes from the level checkpoints' rendered maps."""
+    from .levels import render_levels
+    with torch.no_grad():
+        pkg = render_levels(viewpoint_camera, pc, pipe, bg_color, opt, language_features,
+                            scaling_modifier=scaling_modifier)
+        pkg["relevancy"] = relevancy_map(pkg["language_feature_images"], decoder, pos_embeds, neg_embeds)
+    return pkg
