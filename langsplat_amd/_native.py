@@ -602,6 +602,31 @@ def _f32c_cached(src: torch.Tensor) -> torch.Tensor:
     return c
 
 
+def _fill_forward_args(a: LsrForwardArgs, means3D, shs, colors_precomp, language_feature, opacities, scales,
+                       rotations, cov3D_precomp, raw, flags, shs_rest, out_color, out_language, radii, visible):
+    """The fields of lsr_forward_args every forward sets: the counts P and M (shs_rest included), the
+    raw and forward flags, the inputs, the outputs and the optional visibility output."""
+    a.P = int(means3D.shape[0])
+    a.M = int(shs.shape[1]) if shs is not None and shs.numel() > 0 else 0
+    if shs_rest is not None and shs_rest.numel() > 0:
+        a.M += int(shs_rest.shape[1])
+        a.shs_rest = _ptr(shs_rest)
+    a.raw = int(raw)
+    a.flags = int(flags)
+    a.means3D = _ptr(means3D)
+    a.shs = _ptr(shs)
+    a.colors_precomp = _ptr(colors_precomp)
+    a.language_feature = _ptr(language_feature)
+    a.opacities = _ptr(opacities)
+    a.scales = _ptr(scales)
+    a.rotations = _ptr(rotations)
+    a.cov3D_precomp = _ptr(cov3D_precomp)
+    a.out_color = _ptr(out_color)
+    a.out_language_feature = _ptr(out_language)
+    a.radii = _ptr(radii)
+    a.visible = _ptr(visible)
+
+
 def rasterize_gaussians(rs, means3D, shs, colors_precomp, language_feature, opacities, scales, rotations,
                         cov3D_precomp, raw=0, shs_rest=None, visible=None, loss_target=None, loss_mask=None,
                         out_loss=None, flags=0):
@@ -620,29 +645,11 @@ def rasterize_gaussians(rs, means3D, shs, colors_precomp, language_feature, opac
     color = output_tensor("color", (3, H, W), torch.float32, device)
     lang = output_tensor("language", (3, H, W), torch.float32, device)
     radii = output_tensor("radii", (P,), torch.int32, device)  # preprocess writes every entry
+    if visible is not None and (visible.dtype != torch.bool or visible.numel() != P or not visible.is_contiguous()):
+        raise ValueError("visible must be a contiguous (P,) bool tensor")
     a = LsrForwardArgs()
-    a.P = P
-    a.M = int(shs.shape[1]) if shs is not None and shs.numel() > 0 else 0
-    if shs_rest is not None and shs_rest.numel() > 0:
-        a.M += int(shs_rest.shape[1])
-        a.shs_rest = _ptr(shs_rest)
-    a.raw = int(raw)
-    a.flags = int(flags)
-    a.means3D = _ptr(means3D)
-    a.shs = _ptr(shs)
-    a.colors_precomp = _ptr(colors_precomp)
-    a.language_feature = _ptr(language_feature)
-    a.opacities = _ptr(opacities)
-    a.scales = _ptr(scales)
-    a.rotations = _ptr(rotations)
-    a.cov3D_precomp = _ptr(cov3D_precomp)
-    a.out_color = _ptr(color)
-    a.out_language_feature = _ptr(lang)
-    a.radii = _ptr(radii)
-    if visible is not None:
-        if visible.dtype != torch.bool or visible.numel() != P or not visible.is_contiguous():
-            raise ValueError("visible must be a contiguous (P,) bool tensor")
-        a.visible = _ptr(visible)
+    _fill_forward_args(a, means3D, shs, colors_precomp, language_feature, opacities, scales, rotations,
+                       cov3D_precomp, raw, flags, shs_rest, color, lang, radii, visible)
     if out_loss is not None:
         if loss_target is None or tuple(loss_target.shape) != (3, H, W) or loss_target.dtype != torch.float32 \
                 or not loss_target.is_contiguous():
@@ -677,6 +684,17 @@ def rasterize_gaussians(rs, means3D, shs, colors_precomp, language_feature, opac
             alloc.get(LSR_BUF_IMAGE))
 
 
+def check_level_features(language_features, P: int) -> int:
+    """L of an (L, P, 3) stack of level features, 1 <= L <= MAX_LEVELS; anything else: ValueError."""
+    if not isinstance(language_features, torch.Tensor) or language_features.dim() != 3 \
+            or tuple(language_features.shape[1:]) != (P, 3) \
+            or not 1 <= int(language_features.shape[0]) <= MAX_LEVELS:
+        got = tuple(language_features.shape) if isinstance(language_features, torch.Tensor) else type(language_features)
+        raise ValueError(f"language_features must have shape (L, P, 3) with 1 <= L <= {MAX_LEVELS} and P = {P}, "
+                         f"got {got}")
+    return int(language_features.shape[0])
+
+
 def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_features, opacities, scales, rotations,
                                cov3D_precomp, raw=0, shs_rest=None, with_visibility=False):
     """All language levels of a scene in one inference forward (include/lsr.h lsr_forward_levels):
@@ -687,12 +705,7 @@ def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_featur
     lib = load()
     device = means3D.device
     P = int(means3D.shape[0])
-    if language_features is None or language_features.dim() != 3 or tuple(language_features.shape[1:]) != (P, 3) \
-            or not 1 <= int(language_features.shape[0]) <= MAX_LEVELS:
-        got = None if language_features is None else tuple(language_features.shape)
-        raise ValueError(f"rasterize_gaussians_levels: language_features must have shape (L, P, 3) with "
-                         f"1 <= L <= {MAX_LEVELS} and P = {P}, got {got}")
-    L = int(language_features.shape[0])
+    L = check_level_features(language_features, P)
     H, W = int(rs.image_height), int(rs.image_width)
     keep: list = []
     s = make_settings(rs, keep)
@@ -702,26 +715,8 @@ def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_featur
     radii = torch.empty((P,), dtype=torch.int32, device=device)  # preprocess writes every entry
     visible = torch.empty((P,), dtype=torch.bool, device=device) if with_visibility else None
     la = LsrForwardLevelsArgs()
-    a = la.fwd
-    a.P = P
-    a.M = int(shs.shape[1]) if shs is not None and shs.numel() > 0 else 0
-    if shs_rest is not None and shs_rest.numel() > 0:
-        a.M += int(shs_rest.shape[1])
-        a.shs_rest = _ptr(shs_rest)
-    a.raw = int(raw)
-    a.flags = FWD_NO_BACKWARD
-    a.means3D = _ptr(means3D)
-    a.shs = _ptr(shs)
-    a.colors_precomp = _ptr(colors_precomp)
-    a.language_feature = _ptr(lf)
-    a.opacities = _ptr(opacities)
-    a.scales = _ptr(scales)
-    a.rotations = _ptr(rotations)
-    a.cov3D_precomp = _ptr(cov3D_precomp)
-    a.out_color = _ptr(color)
-    a.out_language_feature = _ptr(langs)
-    a.radii = _ptr(radii)
-    a.visible = _ptr(visible)
+    _fill_forward_args(la.fwd, means3D, shs, colors_precomp, lf, opacities, scales, rotations, cov3D_precomp, raw,
+                       FWD_NO_BACKWARD, shs_rest, color, langs, radii, visible)
     la.levels = L
     if L > 1:
         la.more_language_feature = _ptr(lf[1:])

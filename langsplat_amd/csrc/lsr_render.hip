@@ -107,8 +107,9 @@ __device__ __forceinline__ uint32_t entry_cover(float x, float y, float a, float
 }
 
 // Compacts the batch slots [0, cnt) whose cover mask meets `bits` (the wave's blocks) into
-// list[0, n) as LDS byte offsets 16 e of their 16-B records; returns n.  cnt <= kTilePixels: at most
-// four rounds, unrolled.
+// list[0, n) as LDS byte offsets 16 e of their 16-B records; returns n (wave-uniform).  Slots n ..
+// n + 3 get offset 0, so the walk reads the entries of a step past the list's end without testing
+// (their results are discarded).  cnt <= kTilePixels: at most four rounds, unrolled.
 __device__ __forceinline__ int wave_compact(const uint8_t* sM, int cnt, uint32_t bits, int lane, uint16_t* list)
 {
     int n = 0;
@@ -121,6 +122,8 @@ __device__ __forceinline__ int wave_compact(const uint8_t* sM, int cnt, uint32_t
         if (ov) list[n + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(16 * e);
         n += __popcll(m);
     }
+    n = __builtin_amdgcn_readfirstlane(n);
+    if (lane < 4) list[n + lane] = 0;
     return n;
 }
 
@@ -267,6 +270,122 @@ __device__ __forceinline__ void fwd_pixel_blend(FwdPixel& q, float al, bool ok, 
     }
     lo = go && ok ? o : lo;
     q.T = go ? test_T : -fabsf(q.T);
+}
+
+// ---- the forward walk: the blocks k_render_forward and k_render_forward_levels are built from ----
+// How each block takes its arguments (records by value, callables by const reference) is what keeps
+// k_render_forward's code, to the instruction, what it was with these blocks written out in its body
+// (tools/isa_same.py, profiles/forward_walk_shared.txt): check with it after any change here.
+
+// The record of type R at byte offset o (a slot list's value: 16 x slot) of a batch's LDS array.
+template <class R>
+__device__ __forceinline__ R lds_at(const float4* base, uint32_t o)
+{
+    return *reinterpret_cast<const R*>(reinterpret_cast<const char*>(base) + o);
+}
+
+// Thread t's pixel of the tile (pixel_map), the pixel as floats, the tile's corner and whether the
+// pixel lies inside the image.
+struct TilePixel {
+    int px, py;
+    lsr_f2 pxy;
+    float tx0, ty0;
+    bool inside;
+};
+__device__ __forceinline__ TilePixel tile_pixel(const RenderParams& p, int tile, int t)
+{
+    const int tx = tile % p.gx, ty = tile / p.gx;
+    TilePixel P;
+    pixel_map(tx, ty, t, P.px, P.py);
+    P.pxy = make_f2((float)P.px, (float)P.py);
+    P.tx0 = (float)(tx * kTile);
+    P.ty0 = (float)(ty * kTile);
+    P.inside = P.px < p.W && P.py < p.H;
+    return P;
+}
+
+// Stages the list entry with the gathered records a, b, c in batch slot t: the three records every
+// walk reads, then more() (the caller's records: the feature's rest, further levels), then the
+// entry's cover mask, which is returned.  The order of the LDS stores and the cover test is the
+// training kernel's register budget: leave it.
+template <class More>
+__device__ __forceinline__ uint8_t stage_entry(float4* sA, float4* sB, float4* sC, uint8_t* sM, int t, const float4 a,
+                                               const float4 b, const float4 c, float tx0, float ty0,
+                                               const More& more)
+{
+    const float cut = power_cutoff(b.y);
+    sA[t] = make_float4(a.x, a.y, -0.5f * a.z, -0.5f * b.x);
+    sB[t] = make_float4(a.w, b.y, cut, 0.0f);
+    sC[t] = make_float4(b.z, b.w, c.x, c.y);
+    more();
+    const uint8_t m = (uint8_t)entry_cover(a.x, a.y, a.z, a.w, b.x, cut, tx0, ty0);
+    sM[t] = m;
+    return m;
+}
+
+// The alphas of the entries at offsets oa, ob (ob: only if hb) for the pixel pxy, and their alpha
+// tests.  Per list entry, power, exp and alpha do not depend on the pixel state; two entries' exps
+// run as one packed chain (expf_exact_render2: the same IEEE operations per element).
+__device__ __forceinline__ void walk_pair_alpha(const float4* sA, const float4* sB, const lsr_f2 pxy, uint32_t oa,
+                                                uint32_t ob, bool hb, float& ala, float& alb, bool& oka, bool& okb)
+{
+    const float4 Aa = lds_at<float4>(sA, oa), Ba = lds_at<float4>(sB, oa);
+    const float4 Ab = lds_at<float4>(sA, ob), Bb = lds_at<float4>(sB, ob);
+    // per entry {dx, dy} and {A.z dx, A.w dy} as packed ops on the record's own register pairs
+    const lsr_f2 da = make_f2(Aa.x, Aa.y) - pxy, db = make_f2(Ab.x, Ab.y) - pxy;
+    const lsr_f2 ma = make_f2(Aa.z, Aa.w) * da, mb = make_f2(Ab.z, Ab.w) * db;
+    // power = dx (A.z dx - conic.y dy) + (A.w dy) dy: 4 operations after {A.z dx, A.w dy}
+    // (the oracle's render_pixel / backward_pixel and the backward walk use the same order)
+    const float pwa = fma_(da.x, fma_(-Ba.x, da.y, ma.x), ma.y * da.y);
+    const float pwb = fma_(db.x, fma_(-Bb.x, db.y, mb.x), mb.y * db.y);
+    const lsr_f2 G2 = expf_exact_render2(make_f2(pwa, pwb));
+    ala = fminf(0.99f, Ba.y * G2.x);
+    alb = fminf(0.99f, Bb.y * G2.y);
+    oka = !(pwa > 0.0f || pwa < Ba.z) && !(ala < 1.0f / 255.0f);
+    okb = hb && !(pwb > 0.0f || pwb < Bb.z) && !(alb < 1.0f / 255.0f);
+}
+
+// A wave's walk of its slot list [0, n) of one batch, in pairs (a last odd slot alone), while some
+// pixel of the wave composites: blend(alpha, ok, offset) per entry, in list order.  Only the
+// transmittance test and the blend are sequential; T is the pixel's FwdPixel::T, which blend
+// updates.  Returns the slots visited.
+// The list holds byte offsets, so every record read addresses LDS with the list value itself.  A
+// step's offsets come from one read issued during the previous step, so its record reads do not wait
+// behind them.  One basic block per step (the blends have no branches, the wave's "all done" test
+// closes the iteration), so the next step's offset read stays beside this step's record reads.
+template <class Blend>
+__device__ __forceinline__ int walk_list(const uint16_t* slots, int n, const float4* sA, const float4* sB,
+                                         const lsr_f2 pxy, const float& T, const Blend& blend)
+{
+    int i = 0;
+    const uint32_t* const sL2 = reinterpret_cast<const uint32_t*>(slots);
+    uint32_t oo = sL2[0];
+    if (n > 0 && __ballot(T > 0.0f) != 0ull) do {
+        const uint32_t o0 = oo & 0xFFFFu, o1 = oo >> 16;
+        oo = sL2[(i >> 1) + 1];  // slots i + 2, i + 3 (<= n + 1)
+        float al0, al1;
+        bool ok0, ok1;
+        walk_pair_alpha(sA, sB, pxy, o0, o1, i + 1 < n, al0, al1, ok0, ok1);
+        blend(al0, ok0, o0);
+        blend(al1, ok1, o1);
+        // the next offsets are this iteration's value: the compiler may not defer their read to
+        // the next iteration's start (where the record reads would wait behind it)
+        asm volatile("" : "+v"(oo));
+        i += 2;
+    } while (i < n && __ballot(T > 0.0f) != 0ull);
+    return min(i, n);
+}
+
+// A finished pixel's outputs: its colour over the background (Tf = its final transmittance) and its
+// (level-0) language feature.
+__device__ __forceinline__ void store_pixel(const RenderParams& p, size_t pix, size_t HW, const FwdPixel& q, float Tf)
+{
+    p.out_color[pix] = fma_(Tf, p.bg[0], q.C01.x);
+    p.out_color[HW + pix] = fma_(Tf, p.bg[1], q.C01.y);
+    p.out_color[2 * HW + pix] = fma_(Tf, p.bg[2], q.C2F0.x);
+    p.out_lang[pix] = q.C2F0.y;
+    p.out_lang[HW + pix] = q.F12.x;
+    p.out_lang[2 * HW + pix] = q.F12.y;
 }
 
 // ---- fused language-feature loss (train.py:96-99: Ll1 = l1_loss(lang * mask, gt * mask)) ----
@@ -452,10 +571,11 @@ __device__ __forceinline__ void loss_block_publish(const RenderParams& p, float 
 }
 
 // Output of the tiles without entries among u = j, j + M, ... (background colour, T = 1, no
-// contributors); tiles with entries are skipped (their own workgroups render them).  kLoss: returns
-// the thread's loss share of those pixels (language image 0 there).
-template <bool kLoss>
-__device__ float render_empty_tiles(const RenderParams& p, int j, int M)
+// contributors); tiles with entries are skipped (their own workgroups render them).  more(pix, HW):
+// the caller's further output planes (HW apart) of pixel pix.  kLoss: returns the thread's loss share
+// of those pixels (language image 0 there).
+template <bool kLoss, class More>
+__device__ float render_empty_tiles(const RenderParams& p, int j, int M, const More& more)
 {
     float part = 0.0f;
     const int T = p.gx * p.gy;
@@ -477,6 +597,7 @@ __device__ float render_empty_tiles(const RenderParams& p, int j, int M)
         p.out_lang[pix] = 0.0f;
         p.out_lang[HW + pix] = 0.0f;
         p.out_lang[2 * HW + pix] = 0.0f;
+        more(pix, HW);
         if (kLoss) part += loss_pixel(p, pix, HW, 0.0f, 0.0f, 0.0f);
     }
     return part;
@@ -522,20 +643,15 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
         tile = scheduled_tile((int)blockIdx.x, p.sched_counts + kCntFwdClass, p.sched_lists, T);
         if (tile < 0) {  // past the tiles with entries: fill the empty ones, strided
             const int listed = -1 - tile;
-            const float part = render_empty_tiles<kLoss>(p, (int)blockIdx.x - listed, T - listed);
+            const float part = render_empty_tiles<kLoss>(p, (int)blockIdx.x - listed, T - listed, [](size_t, size_t) {});
             if (kLoss) loss_block_publish(p, part);
             if (kStats) timeline_put(0, t_start, -1);
             return;
         }
     }
     launch_priority((int)blockIdx.x, p.prio);
-    const int tx = tile % p.gx, ty = tile / p.gx;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int px, py;
-    pixel_map(tx, ty, t, px, py);
-    const float pfx = (float)px, pfy = (float)py;
-    const lsr_f2 pxy = make_f2(pfx, pfy);
-    const float tx0 = (float)(tx * kTile), ty0 = (float)(ty * kTile);
+    const auto [px, py, pxy, tx0, ty0, inside] = tile_pixel(p, tile, t);
     PhaseTicks ph;
     if (kStats) {
         ph.begin();
@@ -547,7 +663,6 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
         ph.st[1] = wall_clock64();
     }
     const uint32_t start = range.x, end = range.y;
-    const bool inside = px < p.W && py < p.H;
     if (t == 0) s_last = 0;
     uint32_t nrec = 0;  // split replay: boundaries recorded (kSplitChunk, 2 kSplitChunk, ... up to kSplitMax; uniform)
 
@@ -597,13 +712,8 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
             nrec++;
         }
         if (idx < end) {
-            const float cut = power_cutoff(b.y);
-            sA[t] = make_float4(a.x, a.y, -0.5f * a.z, -0.5f * b.x);
-            sB[t] = make_float4(a.w, b.y, cut, 0.0f);
-            sC[t] = make_float4(b.z, b.w, c.x, c.y);
-            sF[t] = make_float4(c.z, c.w, 0.0f, 0.0f);
-            const uint8_t m = (uint8_t)entry_cover(a.x, a.y, a.z, a.w, b.x, cut, tx0, ty0);
-            sM[t] = m;
+            const uint8_t m = stage_entry(sA, sB, sC, sM, t, a, b, c, tx0, ty0,
+                                          [&] { sF[t] = make_float4(c.z, c.w, 0.0f, 0.0f); });
             if (!p.no_bwd) p.cover[idx] = m;  // for the backward (coalesced: one byte per thread)
         }
         __syncthreads();
@@ -615,64 +725,18 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
             }
         }
         const int cnt = (int)min((uint32_t)kThreads, end - base);
-        const int n = __builtin_amdgcn_readfirstlane(wave_compact(sM, cnt, 1u << wave, lane, sL[wave]));
-        if (lane < 4) sL[wave][n + lane] = 0;
+        const int n = wave_compact(sM, cnt, 1u << wave, lane, sL[wave]);
         __syncthreads();  // list visible to the wave's other lanes
         if (kStats) ph.lap(ph.compact);
         if (idx + kThreads < end) g_next = p.point_list[idx + kThreads];
         const uint32_t lb16 = 16u * (base - start + 1u);  // 16 x (list index of slot 0 + 1)
-        const char* const cA = reinterpret_cast<const char*>(sA);
-        const char* const cB = reinterpret_cast<const char*>(sB);
-        const char* const cC = reinterpret_cast<const char*>(sC);
-        const char* const cF = reinterpret_cast<const char*>(sF);
-        // Per list entry: power, exp and alpha do not depend on the pixel state, only the transmittance
-        // test and the blend are sequential.  Two entries' exps run as one packed chain
-        // (expf_exact_render2: the same IEEE operations per element).  The list holds byte offsets,
-        // so every record read addresses LDS with the list value itself.  A step's offsets come from
-        // one read issued during the previous step, so its record reads do not wait behind them.
         uint32_t lo = 0xFFFFFFFFu;  // offset of the batch's last blended entry, per lane
-        // the alpha of the entries at offsets oa, ob (ob: only if hb) and their alpha tests
-        auto pair_alpha = [&](uint32_t oa, uint32_t ob, bool hb, float& ala, float& alb, bool& oka, bool& okb) {
-            const float4 Aa = *reinterpret_cast<const float4*>(cA + oa), Ba = *reinterpret_cast<const float4*>(cB + oa);
-            const float4 Ab = *reinterpret_cast<const float4*>(cA + ob), Bb = *reinterpret_cast<const float4*>(cB + ob);
-            // per entry {dx, dy} and {A.z dx, A.w dy} as packed ops on the record's own register pairs
-            const lsr_f2 da = make_f2(Aa.x, Aa.y) - pxy, db = make_f2(Ab.x, Ab.y) - pxy;
-            const lsr_f2 ma = make_f2(Aa.z, Aa.w) * da, mb = make_f2(Ab.z, Ab.w) * db;
-            // power = dx (A.z dx - conic.y dy) + (A.w dy) dy: 4 operations after {A.z dx, A.w dy}
-            // (the oracle's render_pixel / backward_pixel and the backward walk use the same order)
-            const float pwa = fma_(da.x, fma_(-Ba.x, da.y, ma.x), ma.y * da.y);
-            const float pwb = fma_(db.x, fma_(-Bb.x, db.y, mb.x), mb.y * db.y);
-            const lsr_f2 G2 = expf_exact_render2(make_f2(pwa, pwb));
-            ala = fminf(0.99f, Ba.y * G2.x);
-            alb = fminf(0.99f, Bb.y * G2.y);
-            oka = !(pwa > 0.0f || pwa < Ba.z) && !(ala < 1.0f / 255.0f);
-            okb = hb && !(pwb > 0.0f || pwb < Bb.z) && !(alb < 1.0f / 255.0f);
-        };
-        auto blend_at = [&](float al, bool ok, uint32_t o) {
-            const float4 Cc = *reinterpret_cast<const float4*>(cC + o);
-            const lsr_f2 Ff = kFeat ? *reinterpret_cast<const lsr_f2*>(cF + o) : make_f2(0.f, 0.f);
+        const int visited = walk_list(sL[wave], n, sA, sB, pxy, q.T, [&](float al, bool ok, uint32_t o) {
+            const float4 Cc = lds_at<float4>(sC, o);
+            const lsr_f2 Ff = kFeat ? lds_at<lsr_f2>(sF, o) : make_f2(0.f, 0.f);
             fwd_pixel_blend<kFeat>(q, al, ok, o, lo, Cc, Ff);
-        };
-        // one basic block per step (the blends have no branches, the wave's "all done" test closes the
-        // iteration), so the next step's offset read stays beside this step's record reads
-        int i = 0;
-        // the pairs of list slots [0, n) (a last odd slot alone)
-        const uint32_t* const sL2 = reinterpret_cast<const uint32_t*>(sL[wave]);
-        uint32_t oo = sL2[0];
-        if (n > 0 && __ballot(q.T > 0.0f) != 0ull) do {
-            const uint32_t o0 = oo & 0xFFFFu, o1 = oo >> 16;
-            oo = sL2[(i >> 1) + 1];  // slots i + 2, i + 3 (<= n + 1)
-            float al0, al1;
-            bool ok0, ok1;
-            pair_alpha(o0, o1, i + 1 < n, al0, al1, ok0, ok1);
-            blend_at(al0, ok0, o0);
-            blend_at(al1, ok1, o1);
-            // the next offsets are this iteration's value: the compiler may not defer their read to
-            // the next iteration's start (where the record reads would wait behind it)
-            asm volatile("" : "+v"(oo));
-            i += 2;
-        } while (i < n && __ballot(q.T > 0.0f) != 0ull);
-        const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(min(i, n));
+        });
+        const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane(visited);
         if (bi == 0) wk0 = wv;
         else if (bi == 1) wk1 = wv;
         else if (bi == 2) wk2 = wv;
@@ -745,12 +809,7 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
             p.final_T[pix] = Tf;
             p.n_contrib[pix] = qlast;
         }
-        p.out_color[pix] = fma_(Tf, p.bg[0], q.C01.x);
-        p.out_color[HW + pix] = fma_(Tf, p.bg[1], q.C01.y);
-        p.out_color[2 * HW + pix] = fma_(Tf, p.bg[2], q.C2F0.x);
-        p.out_lang[pix] = q.C2F0.y;
-        p.out_lang[HW + pix] = q.F12.x;
-        p.out_lang[2 * HW + pix] = q.F12.y;
+        store_pixel(p, pix, HW, q, Tf);
     }
     if (kLoss) loss_block_publish(p, part);
 }
@@ -878,12 +937,13 @@ hipError_t launch_render_forward(const RenderParams& pin, int tiles, hipStream_t
 // ------------------------------------------------------------------------------------------
 // multi-level inference forward (lsr_forward_levels)
 // ------------------------------------------------------------------------------------------
-// k_render_forward's walk -- the same tile ownership and schedule, 256-entry batches, cover masks,
-// compacted lists, paired exps and alpha / stop tests, so the same blend weights w = alpha T in the
-// same order -- carrying kE = 3 (kLevels - 1) more feature sums per pixel.  Each is its own
-// fma(f, w, acc) chain (packed in pairs: the same IEEE operation per element), so every level's map
-// is the single-level forward's for that level's features.  Inference only: no cover bytes, split
-// states, work lists, final_T or n_contrib.
+// k_render_forward's walk, built from the same blocks (tile_pixel, stage_entry, wave_compact,
+// walk_list, store_pixel, render_empty_tiles) -- the same tile ownership and schedule, 256-entry
+// batches, cover masks, compacted lists, paired exps and alpha / stop tests, so the same blend weights
+// w = alpha T in the same order -- carrying kE = 3 (kLevels - 1) more feature sums per pixel.  Each
+// is its own fma(f, w, acc) chain (packed in pairs: the same IEEE operation per element), so every
+// level's map is the single-level forward's for that level's features.  Inference only: no cover
+// bytes, split states, work lists, final_T or n_contrib.
 //
 // Extra features e = 3 (level - 1) + channel of a batch slot: e0, e1 in the two spare floats of the
 // slot's sF record, e2..e5 in sX0, e6..e8 in sX1 (kLevels == 4 only; at kLevels == 2 one float per
@@ -925,27 +985,6 @@ __device__ __forceinline__ void levels_pixel_blend(FwdPixel& q, LevelSums<kLevel
     q.T = go ? test_T : -fabsf(q.T);
 }
 
-// render_empty_tiles for this form: background colour and zeros in every level
-__device__ void render_empty_tiles_levels(const RenderLevelsParams& lp, int j, int M)
-{
-    const RenderParams& p = lp.r;
-    const int T = p.gx * p.gy;
-    const size_t HW = (size_t)p.W * p.H;
-    for (int u = j; u < T; u += M) {
-        const uint2 r = p.ranges[u];
-        if (r.x != r.y) continue;
-        int px, py;
-        pixel_map(u % p.gx, u / p.gx, (int)threadIdx.x, px, py);
-        if (!(px < p.W && py < p.H)) continue;
-        const size_t pix = (size_t)py * p.W + px;
-        p.out_color[pix] = fma_(1.0f, p.bg[0], 0.0f);
-        p.out_color[HW + pix] = fma_(1.0f, p.bg[1], 0.0f);
-        p.out_color[2 * HW + pix] = fma_(1.0f, p.bg[2], 0.0f);
-        for (int c = 0; c < 3; c++) p.out_lang[c * HW + pix] = 0.0f;
-        for (int e = 0; e < 3 * (lp.levels - 1); e++) lp.out_more[e * HW + pix] = 0.0f;
-    }
-}
-
 // Waves per SIMD the kernel is compiled for: the single-level forward's 7 (<= 72 VGPRs) up to three
 // levels; the 9 extra sums and two more staged float4s of four levels take it past 72 (it would
 // spill in the walk), and its LDS allows 6 workgroups per CU anyway.
@@ -970,25 +1009,24 @@ __global__ __launch_bounds__(kTilePixels, kLevelsWaves<kLevels>) void k_render_f
 
     const int T = p.gx * p.gy;
     int tile = (int)blockIdx.x;
+    // (k_render_forward's tile choice, written out in both: as a shared block with the empty-tile fill
+    // as a callable, or one returning a "no tile" answer, the return costs the training kernels an
+    // exec-mask round trip and other spills)
     if (p.sched_counts) {
         tile = scheduled_tile((int)blockIdx.x, p.sched_counts + kCntFwdClass, p.sched_lists, T);
-        if (tile < 0) {  // past the tiles with entries: fill the empty ones, strided
+        if (tile < 0) {  // past the tiles with entries: fill the empty ones, strided, with zeros in every level
             const int listed = -1 - tile;
-            render_empty_tiles_levels(lp, (int)blockIdx.x - listed, T - listed);
+            render_empty_tiles<false>(p, (int)blockIdx.x - listed, T - listed, [&](size_t pix, size_t HW) {
+                for (int e = 0; e < 3 * (lp.levels - 1); e++) lp.out_more[e * HW + pix] = 0.0f;
+            });
             return;
         }
     }
     launch_priority((int)blockIdx.x, p.prio);
-    const int tx = tile % p.gx, ty = tile / p.gx;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    int px, py;
-    pixel_map(tx, ty, t, px, py);
-    const float pfx = (float)px, pfy = (float)py;
-    const lsr_f2 pxy = make_f2(pfx, pfy);
-    const float tx0 = (float)(tx * kTile), ty0 = (float)(ty * kTile);
+    const auto [px, py, pxy, tx0, ty0, inside] = tile_pixel(p, tile, t);
     const uint2 range = p.ranges[tile];
     const uint32_t start = range.x, end = range.y;
-    const bool inside = px < p.W && py < p.H;
 
     FwdPixel q{inside ? 1.0f : -1.0f, make_f2(0.f, 0.f), make_f2(0.f, 0.f), make_f2(0.f, 0.f), 0u, 0u};
     LevelSums<kLevels> x;
@@ -1009,74 +1047,30 @@ __global__ __launch_bounds__(kTilePixels, kLevelsWaves<kLevels>) void k_render_f
             const float4 l0 = lv[0];
             const float4 l1 = kQ > 1 ? lv[1] : make_float4(0.f, 0.f, 0.f, 0.f);
             const float4 l2 = kQ > 2 ? lv[2] : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float cut = power_cutoff(b.y);
-            sA[t] = make_float4(a.x, a.y, -0.5f * a.z, -0.5f * b.x);
-            sB[t] = make_float4(a.w, b.y, cut, 0.0f);
-            sC[t] = make_float4(b.z, b.w, c.x, c.y);
-            sF[t] = make_float4(c.z, c.w, l0.x, l0.y);
-            sX0[t] = make_float4(l0.z, l0.w, l1.x, l1.y);
-            if (kLevels == 4) sX1[t] = make_float4(l1.z, l1.w, l2.x, 0.0f);
-            sM[t] = (uint8_t)entry_cover(a.x, a.y, a.z, a.w, b.x, cut, tx0, ty0);
+            stage_entry(sA, sB, sC, sM, t, a, b, c, tx0, ty0, [&] {
+                sF[t] = make_float4(c.z, c.w, l0.x, l0.y);
+                sX0[t] = make_float4(l0.z, l0.w, l1.x, l1.y);
+                if (kLevels == 4) sX1[t] = make_float4(l1.z, l1.w, l2.x, 0.0f);
+            });
         }
         __syncthreads();
         const int cnt = (int)min((uint32_t)kThreads, end - base);
-        const int n = __builtin_amdgcn_readfirstlane(wave_compact(sM, cnt, 1u << wave, lane, sL[wave]));
-        if (lane < 4) sL[wave][n + lane] = 0;
+        const int n = wave_compact(sM, cnt, 1u << wave, lane, sL[wave]);
         __syncthreads();  // list visible to the wave's other lanes
         if (idx + kThreads < end) g_next = p.point_list[idx + kThreads];
-        const char* const cA = reinterpret_cast<const char*>(sA);
-        const char* const cB = reinterpret_cast<const char*>(sB);
-        const char* const cC = reinterpret_cast<const char*>(sC);
-        const char* const cF = reinterpret_cast<const char*>(sF);
-        const char* const cX0 = reinterpret_cast<const char*>(sX0);
-        const char* const cX1 = reinterpret_cast<const char*>(sX1);
-        // k_render_forward's pair_alpha: the same operations on the same records
-        auto pair_alpha = [&](uint32_t oa, uint32_t ob, bool hb, float& ala, float& alb, bool& oka, bool& okb) {
-            const float4 Aa = *reinterpret_cast<const float4*>(cA + oa), Ba = *reinterpret_cast<const float4*>(cB + oa);
-            const float4 Ab = *reinterpret_cast<const float4*>(cA + ob), Bb = *reinterpret_cast<const float4*>(cB + ob);
-            const lsr_f2 da = make_f2(Aa.x, Aa.y) - pxy, db = make_f2(Ab.x, Ab.y) - pxy;
-            const lsr_f2 ma = make_f2(Aa.z, Aa.w) * da, mb = make_f2(Ab.z, Ab.w) * db;
-            const float pwa = fma_(da.x, fma_(-Ba.x, da.y, ma.x), ma.y * da.y);
-            const float pwb = fma_(db.x, fma_(-Bb.x, db.y, mb.x), mb.y * db.y);
-            const lsr_f2 G2 = expf_exact_render2(make_f2(pwa, pwb));
-            ala = fminf(0.99f, Ba.y * G2.x);
-            alb = fminf(0.99f, Bb.y * G2.y);
-            oka = !(pwa > 0.0f || pwa < Ba.z) && !(ala < 1.0f / 255.0f);
-            okb = hb && !(pwb > 0.0f || pwb < Bb.z) && !(alb < 1.0f / 255.0f);
-        };
-        auto blend_at = [&](float al, bool ok, uint32_t o) {
-            const float4 Cc = *reinterpret_cast<const float4*>(cC + o);
-            const float4 Ff = *reinterpret_cast<const float4*>(cF + o);
-            const float4 X0 = kLevels == 2 ? make_float4(*reinterpret_cast<const float*>(cX0 + o), 0.f, 0.f, 0.f)
-                                           : *reinterpret_cast<const float4*>(cX0 + o);
-            const float4 X1 = kLevels == 4 ? *reinterpret_cast<const float4*>(cX1 + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+        walk_list(sL[wave], n, sA, sB, pxy, q.T, [&](float al, bool ok, uint32_t o) {
+            const float4 Cc = lds_at<float4>(sC, o);
+            const float4 Ff = lds_at<float4>(sF, o);
+            const float4 X0 = kLevels == 2 ? make_float4(lds_at<float>(sX0, o), 0.f, 0.f, 0.f)
+                                           : lds_at<float4>(sX0, o);
+            const float4 X1 = kLevels == 4 ? lds_at<float4>(sX1, o) : make_float4(0.f, 0.f, 0.f, 0.f);
             levels_pixel_blend<kLevels>(q, x, al, ok, Cc, Ff, X0, X1);
-        };
-        int i = 0;
-        const uint32_t* const sL2 = reinterpret_cast<const uint32_t*>(sL[wave]);
-        uint32_t oo = sL2[0];
-        if (n > 0 && __ballot(q.T > 0.0f) != 0ull) do {
-            const uint32_t o0 = oo & 0xFFFFu, o1 = oo >> 16;
-            oo = sL2[(i >> 1) + 1];  // slots i + 2, i + 3 (<= n + 1)
-            float al0, al1;
-            bool ok0, ok1;
-            pair_alpha(o0, o1, i + 1 < n, al0, al1, ok0, ok1);
-            blend_at(al0, ok0, o0);
-            blend_at(al1, ok1, o1);
-            asm volatile("" : "+v"(oo));  // (k_render_forward: the next offsets' read stays in this step)
-            i += 2;
-        } while (i < n && __ballot(q.T > 0.0f) != 0ull);
+        });
     }
     if (!inside) return;
     const size_t HW = (size_t)p.W * p.H;
     const size_t pix = (size_t)py * p.W + px;
-    const float Tf = fabsf(q.T);
-    p.out_color[pix] = fma_(Tf, p.bg[0], q.C01.x);
-    p.out_color[HW + pix] = fma_(Tf, p.bg[1], q.C01.y);
-    p.out_color[2 * HW + pix] = fma_(Tf, p.bg[2], q.C2F0.x);
-    p.out_lang[pix] = q.C2F0.y;
-    p.out_lang[HW + pix] = q.F12.x;
-    p.out_lang[2 * HW + pix] = q.F12.y;
+    store_pixel(p, pix, HW, q, fabsf(q.T));
     float* const om = lp.out_more + pix;  // extra e at om[e HW]
 #pragma unroll
     for (int k = 0; k < LevelSums<kLevels>::kPairs; k++) {

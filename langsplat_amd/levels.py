@@ -11,14 +11,12 @@ Inference only: there is no backward.  There is no CPU path: a CPU tensor raises
 """
 from __future__ import annotations
 
-import math
 from typing import Sequence
 
 import torch
 
 from . import _native
-from .rasterizer import GaussianRasterizationSettings
-from .render import _fusable, eval_sh
+from .render import _fusable, camera_settings, unfused_inputs
 
 _GEOMETRY = ("_xyz", "_features_dc", "_features_rest", "_opacity", "_scaling", "_rotation")
 
@@ -51,15 +49,6 @@ def stack_levels(models: Sequence):
     return first, torch.stack(feats, dim=0)
 
 
-def _check_features(language_features, P: int):
-    if not isinstance(language_features, torch.Tensor) or language_features.dim() != 3 \
-            or tuple(language_features.shape[1:]) != (P, 3) \
-            or not 1 <= int(language_features.shape[0]) <= _native.MAX_LEVELS:
-        got = tuple(language_features.shape) if isinstance(language_features, torch.Tensor) else type(language_features)
-        raise ValueError(f"render_levels: language_features must have shape (L, P, 3) with 1 <= L <= "
-                         f"{_native.MAX_LEVELS} and P = {P}, got {got}")
-
-
 def _f32(t):
     return None if t is None else _native._f32c(t.detach())
 
@@ -76,27 +65,13 @@ def render_levels(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, opt, langu
     Always runs under torch.no_grad(): no output requires grad."""
     xyz = pc.get_xyz
     P = int(xyz.shape[0])
-    _check_features(language_features, P)
+    _native.check_level_features(language_features, P)
     if xyz.device.type != "cuda" or language_features.device.type != "cuda":
         raise RuntimeError("render_levels: inputs must be on a ROCm GPU device "
                            f"(got {xyz.device}, {language_features.device}); there is no CPU implementation")
     if not opt.include_feature:
         raise ValueError("render_levels: needs opt.include_feature")
-    rs = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height),
-        image_width=int(viewpoint_camera.image_width),
-        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
-        tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-        bg=bg_color,
-        scale_modifier=scaling_modifier,
-        viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform,
-        sh_degree=pc.active_sh_degree,
-        campos=viewpoint_camera.camera_center,
-        prefiltered=False,
-        debug=pipe.debug,
-        include_feature=True,
-    )
+    rs = camera_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, True)
     lf = language_features.detach()
     if _fusable(pc, pipe, override_color, xyz.device):
         raw = _native.RAW_OPACITY | _native.RAW_SCALES | _native.RAW_ROTATIONS | _native.RAW_LANGUAGE
@@ -107,26 +82,12 @@ def render_levels(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, opt, langu
         return {"render": color, "language_feature_images": langs, "radii": radii, "visibility_filter": visible}
 
     # the unfused call of render(): activated inputs, the language normalisation in torch
-    scales = rotations = cov3D_precomp = None
-    if pipe.compute_cov3D_python:
-        cov3D_precomp = pc.get_covariance(scaling_modifier)
-    else:
-        scales, rotations = pc.get_scaling, pc.get_rotation
-    shs = colors_precomp = None
-    if override_color is None:
-        if pipe.convert_SHs_python:
-            shs_view = pc.get_features.transpose(1, 2).view(-1, 3, (pc.max_sh_degree + 1) ** 2)
-            dir_pp = xyz - viewpoint_camera.camera_center.repeat(pc.get_features.shape[0], 1)
-            dir_pp_normalized = dir_pp / dir_pp.norm(dim=1, keepdim=True)
-            colors_precomp = torch.clamp_min(eval_sh(pc.active_sh_degree, shs_view, dir_pp_normalized) + 0.5, 0.0)
-        else:
-            shs = pc.get_features
-    else:
-        colors_precomp = override_color
+    _, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = unfused_inputs(
+        viewpoint_camera, pc, pipe, scaling_modifier, override_color)
     # per level, on a contiguous (P, 3) tensor: the very operations (and reduction shapes) of render()
     lf = torch.stack([x / (x.norm(dim=-1, keepdim=True) + 1e-9) for x in _f32(lf)], dim=0)
     _, color, langs, radii = _native.rasterize_gaussians_levels(
-        rs, _f32(xyz), _f32(shs), _f32(colors_precomp), lf, _f32(pc.get_opacity), _f32(scales), _f32(rotations),
+        rs, _f32(xyz), _f32(shs), _f32(colors_precomp), lf, _f32(opacity), _f32(scales), _f32(rotations),
         _f32(cov3D_precomp), raw=0)
     return {"render": color, "language_feature_images": langs, "radii": radii, "visibility_filter": radii > 0}
 

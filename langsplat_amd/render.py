@@ -78,21 +78,13 @@ def _screenspace_points(xyz: torch.Tensor) -> torch.Tensor:
     return z.detach().requires_grad_(True)
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, opt, scaling_modifier=1.0, override_color=None,
-           language_target=None):
-    """gaussian_renderer/__init__.py:19-115.  language_target=(gt, mask) -- what
-    Camera.get_language_feature returns (scene/cameras.py:58-92), e.g. from loss.LanguageFeatureCache
-    -- additionally returns "language_l1" = l1_loss(language_feature_image * mask, gt * mask), the
-    language loss of train.py:96-99, computed inside the rasterizer kernels (SURVEY.md §8f row f2)."""
-    screenspace_points = _screenspace_points(pc.get_xyz)
-
-    tanfovx = math.tan(viewpoint_camera.FoVx * 0.5)
-    tanfovy = math.tan(viewpoint_camera.FoVy * 0.5)
-    raster_settings = GaussianRasterizationSettings(
+def camera_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, include_feature):
+    """The rasterizer settings of one view (gaussian_renderer/__init__.py:34-51)."""
+    return GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height),
         image_width=int(viewpoint_camera.image_width),
-        tanfovx=tanfovx,
-        tanfovy=tanfovy,
+        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
+        tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
         bg=bg_color,
         scale_modifier=scaling_modifier,
         viewmatrix=viewpoint_camera.world_view_transform,
@@ -101,28 +93,15 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, opt, scaling_modi
         campos=viewpoint_camera.camera_center,
         prefiltered=False,
         debug=pipe.debug,
-        include_feature=opt.include_feature,
+        include_feature=include_feature,
     )
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
 
-    if _fusable(pc, pipe, override_color, screenspace_points.device):
-        lang_raw = pc.get_language_feature if opt.include_feature else None
-        fused = rasterize_gaussians_fused(
-            pc.get_xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling,
-            pc._rotation, lang_raw, raster_settings, with_visibility=True,
-            language_target=language_target if opt.include_feature else None)
-        rendered_image, language_feature_image, radii, visible = fused[:4]
-        pkg = {"render": rendered_image,
-               "language_feature_image": language_feature_image,
-               "viewspace_points": screenspace_points,
-               "visibility_filter": visible,  # radii > 0, from the preprocess kernel
-               "radii": radii}
-        if language_target is not None:
-            pkg["language_l1"] = fused[4] if opt.include_feature else _l1(language_feature_image, *language_target)
-        return pkg
 
+def unfused_inputs(viewpoint_camera, pc, pipe, scaling_modifier, override_color):
+    """The activated inputs of the unfused rasterizer call (gaussian_renderer/__init__.py:55-85):
+    (means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp), of which the pipe's
+    compute_cov3D_python / convert_SHs_python switches and override_color leave some None."""
     means3D = pc.get_xyz
-    means2D = screenspace_points
     opacity = pc.get_opacity
     scales = rotations = cov3D_precomp = None
     if pipe.compute_cov3D_python:
@@ -142,6 +121,38 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, opt, scaling_modi
             shs = pc.get_features
     else:
         colors_precomp = override_color
+    return means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp
+
+
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, opt, scaling_modifier=1.0, override_color=None,
+           language_target=None):
+    """gaussian_renderer/__init__.py:19-115.  language_target=(gt, mask) -- what
+    Camera.get_language_feature returns (scene/cameras.py:58-92), e.g. from loss.LanguageFeatureCache
+    -- additionally returns "language_l1" = l1_loss(language_feature_image * mask, gt * mask), the
+    language loss of train.py:96-99, computed inside the rasterizer kernels (SURVEY.md §8f row f2)."""
+    screenspace_points = _screenspace_points(pc.get_xyz)
+    raster_settings = camera_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier, opt.include_feature)
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+
+    if _fusable(pc, pipe, override_color, screenspace_points.device):
+        lang_raw = pc.get_language_feature if opt.include_feature else None
+        fused = rasterize_gaussians_fused(
+            pc.get_xyz, screenspace_points, pc._features_dc, pc._features_rest, pc._opacity, pc._scaling,
+            pc._rotation, lang_raw, raster_settings, with_visibility=True,
+            language_target=language_target if opt.include_feature else None)
+        rendered_image, language_feature_image, radii, visible = fused[:4]
+        pkg = {"render": rendered_image,
+               "language_feature_image": language_feature_image,
+               "viewspace_points": screenspace_points,
+               "visibility_filter": visible,  # radii > 0, from the preprocess kernel
+               "radii": radii}
+        if language_target is not None:
+            pkg["language_l1"] = fused[4] if opt.include_feature else _l1(language_feature_image, *language_target)
+        return pkg
+
+    means2D = screenspace_points
+    means3D, opacity, scales, rotations, cov3D_precomp, shs, colors_precomp = unfused_inputs(
+        viewpoint_camera, pc, pipe, scaling_modifier, override_color)
     if opt.include_feature:
         ready = _native.language_ready.active()
         if ready is not None:

@@ -1,0 +1,68 @@
+"""Are the kernels of two hipcc -S listings the same code? (measurement aid; sibling of isa_loop.py)
+
+    hipcc --offload-arch=gfx950 ... --cuda-device-only -S -o old.s langsplat_amd/csrc/lsr_render.hip
+    python3 tools/isa_same.py old.s new.s [name-substring]
+
+Per kernel of either listing: the instruction counts, whether the two mnemonic sequences are
+identical (operands, hence register names and label numbers, are not compared) and whether the
+resource figures the listing records are: VGPRs, SGPRs, scratch bytes per lane, VGPR and SGPR
+spills, waves per SIMD and static LDS bytes.
+"""
+import re
+import shutil
+import subprocess
+import sys
+
+INFO = {"NumVgprs": "vgpr", "TotalNumSgprs": "sgpr", "ScratchSize": "scratch", "Occupancy": "waves",
+        "LDSByteSize": "lds"}
+FIGURES = ["vgpr", "sgpr", "scratch", "vspill", "sspill", "waves", "lds"]
+
+
+def kernels(path):
+    """{symbol: ([mnemonic, ...], {figure: value})} of the listing's functions, in its order."""
+    out, name, body, last, funcs = {}, None, False, None, set()
+    for l in open(path):
+        if m := re.match(r"^\s+\.type\s+(\w+),@function", l):
+            funcs.add(m.group(1))
+        elif (m := re.match(r"^(_Z\w+):", l)) and m.group(1) in funcs:
+            name = last = m.group(1)
+            out[name], body = ([], {}), True
+        elif l.startswith(".Lfunc_end"):
+            body = False
+        elif body:
+            s = l.split(";")[0].strip()
+            if s and not s.startswith(".") and not s.endswith(":"):
+                out[name][0].append(s.split()[0])
+        elif (m := re.match(r"^; (\w+): (\d+)", l)) and m.group(1) in INFO and last:
+            out[last][1][INFO[m.group(1)]] = int(m.group(2))
+        elif (m := re.match(r"^\s+\.name:\s+(\S+)", l)) and m.group(1) in out:  # the metadata follows all code
+            last = m.group(1)
+        elif (m := re.match(r"^\s+\.([sv])gpr_spill_count:\s+(\d+)", l)) and last in out:
+            out[last][1][m.group(1) + "spill"] = int(m.group(2))
+    return out
+
+
+def demangle(names):
+    tool = shutil.which("llvm-cxxfilt") or shutil.which("c++filt")
+    if not tool or not names:
+        return dict(zip(names, names))
+    got = subprocess.run([tool] + names, capture_output=True, text=True).stdout.split("\n")
+    return {n: re.sub(r"^void |lsr::|\(lsr::\w+\)$", "", g) for n, g in zip(names, got)}
+
+
+def main():
+    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    want = sys.argv[3] if len(sys.argv) > 3 else ""
+    names = [n for n in dict.fromkeys(list(old) + list(new)) if want in n]
+    pretty = demangle(names)
+    print(f"{'kernel':<48} {'instr old':>9} {'new':>6}  sequence   figures (" + " ".join(FIGURES) + ")")
+    for n in names:
+        (io, fo), (inw, fn) = old.get(n, ([], {})), new.get(n, ([], {}))
+        seq = "only old" if n not in new else "only new" if n not in old else "identical" if io == inw else "DIFFERS"
+        fig = lambda f: " ".join(str(f.get(k, "-")) for k in FIGURES)
+        figs = f"same: {fig(fn)}" if fo == fn else f"{fig(fo)} -> {fig(fn)}"
+        print(f"{pretty[n]:<48} {len(io):>9} {len(inw):>6}  {seq:<9}  {figs}")
+
+
+if __name__ == "__main__":
+    main()
