@@ -704,6 +704,71 @@ int32_t lsr_forward_levels(const lsr_settings* settings, const lsr_forward_level
  * its registers and LDS with the hardware's allocation granules; negative (-lsr_status) on error. */
 int32_t lsr_debug_levels_occupancy(int32_t levels);
 
+/* ---- a view's frozen geometry, kept across steps of the language stage ---------------------------
+ * In the language stage every geometry parameter is frozen (scene/gaussian_model.py:203-217), and
+ * train.py:85-87 draws each of a scene's views again every epoch: for one camera, what a
+ * LSR_PHASE_GEOMETRY forward (preprocess, depth order, binning) leaves behind is the same at every
+ * visit.  lsr_view_save gathers the part of it that later phases read into a compact pack;
+ * lsr_view_restore puts a pack back into a buffer set of the same P, image size and capacities, in
+ * place of the geometry call (langsplat_amd/pipeline.py PipelinedGraphStep's view cache).
+ *
+ * The pack (lsr_view_pack_bytes; every segment 16-byte aligned, sizes rounded up to 16 bytes, in
+ * this order; T = the number of 16 x 16 tiles):
+ *     320 B    the counter slots and the forward's 64 class counts of the longest-first schedule
+ *     32 P     record[3 i], record[3 i + 1] of every Gaussian (lsr_state_layout.record)
+ *     4 P      word 0 (b) of record[3 i + 2]
+ *     4 P      radii
+ *     4 P      clamped
+ *     8 T      ranges
+ *     4 T      the forward's scheduled tiles, class by class
+ *     4 R      the num_rendered point-list entries
+ * i.e. what LSR_PHASE_COMPOSITE[_FILLED], lsr_backward (with or without geometry gradients) and
+ * lsr_language_tail read of the geometry phase's products.  Sort and scan scratch, depth keys and
+ * super-tile tables are not kept, nor what the compositing writes (cover bytes, split states, the
+ * backward's work lists, final_T, n_contrib), nor the records' language slots.
+ *
+ * lsr_view_save reads a buffer set that a capacity-mode LSR_PHASE_GEOMETRY forward filled (the
+ * compositing and backward of that view may have run on it since) whose view fitted its capacities;
+ * num_rendered is that view's count (counter slot 1, read back by the caller).  lsr_view_restore
+ * brings a set into the state that geometry call would leave, for everything a later phase reads;
+ * it also re-initialises what the geometry phase clears on every run and a later phase relies on:
+ * the fused loss's words, the forward flags (from `flags` and `fused_loss`, as the geometry call
+ * publishes them), the overflow word and *overflow (0), and the backward's class counts (0).  It
+ * never writes the records' language slots: a fused update's fill_record may fill them before,
+ * while or after the restore runs, exactly as with the geometry call.
+ *
+ * One kernel launch per call on `stream`; neither call waits for the device.  LSR_ERR_INVALID before
+ * any device work for null args or a null geom / image / binning / radii / pack, P, width, height or
+ * a capacity < 1, num_rendered < 0 or > capacity_rendered, pack_bytes < lsr_view_pack_bytes(...), a
+ * buffer or pack that is not 16-byte aligned, or an unknown flag.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect them by symbol. */
+typedef struct lsr_view_args {
+    int32_t P, width, height;
+    int32_t flags;                /* restore: the lsr_forward_flags of the forward this set serves */
+    int32_t fused_loss;           /* restore: that forward fuses the loss (out_loss with the feature) */
+    int32_t reserved;             /* 0 */
+    int64_t capacity_rendered;    /* the set's capacities (lsr_forward_args) */
+    int64_t capacity_entries;
+    int64_t num_rendered;         /* the view's tile instances */
+    void* geom;                   /* the set's LSR_BUF_GEOM, LSR_BUF_IMAGE and LSR_BUF_BINNING buffers */
+    void* image;
+    void* binning;
+    int32_t* radii;               /* P: the forward's radii output */
+    void* pack;                   /* device, pack_bytes bytes */
+    size_t pack_bytes;
+    int32_t* overflow;            /* restore: NULL, or the forward's overflow flag (set to 0) */
+} lsr_view_args;
+size_t lsr_view_pack_bytes(int32_t P, int32_t width, int32_t height, int64_t num_rendered);
+/* The eight counter slots a capacity-mode geometry call left in `image` (the set's LSR_BUF_IMAGE
+ * buffer of a width x height forward; slot 1 = num_rendered, slot 7 = the overflow word) into
+ * host_counters: 8 x uint32 of pinned host memory the device can write, by one one-wave kernel on
+ * `stream` -- no copy engine, no wait; the values are there once an event recorded after the call
+ * has completed.  How a caller learns the num_rendered lsr_view_save needs without reading the
+ * device.  LSR_ERR_INVALID for a null pointer or a size < 1. */
+int32_t lsr_view_counts(int32_t width, int32_t height, const void* image, uint32_t* host_counters, void* stream);
+int32_t lsr_view_save(const lsr_view_args* args, void* stream);
+int32_t lsr_view_restore(const lsr_view_args* args, void* stream);
+
 size_t lsr_masked_l1_scratch_bytes(int32_t C, int64_t HW);
 int32_t lsr_masked_l1_forward(int32_t C, int64_t HW, const float* pred, const float* gt, const void* mask,
                               int32_t mask_is_float, float* loss, void* scratch, void* stream);

@@ -133,6 +133,14 @@ class LsrRgbLossBwdArgs(ctypes.Structure):
                 ("dL_dloss", _vp), ("out_dL_dimage", _vp)]
 
 
+class LsrViewArgs(ctypes.Structure):
+    _fields_ = [("P", ctypes.c_int32), ("width", ctypes.c_int32), ("height", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("fused_loss", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("capacity_rendered", ctypes.c_int64), ("capacity_entries", ctypes.c_int64),
+                ("num_rendered", ctypes.c_int64), ("geom", _vp), ("image", _vp), ("binning", _vp), ("radii", _vp),
+                ("pack", _vp), ("pack_bytes", ctypes.c_size_t), ("overflow", _vp)]
+
+
 ALLOC_FN = ctypes.CFUNCTYPE(_vp, _vp, ctypes.c_int32, ctypes.c_size_t)
 
 # symbol -> (restype, argtypes); must cover every function declared in include/lsr.h
@@ -160,6 +168,10 @@ SIGNATURES = {
     "lsr_rgb_loss_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
     "lsr_rgb_loss_forward": (ctypes.c_int32, [ctypes.POINTER(LsrRgbLossArgs), _vp]),
     "lsr_rgb_loss_backward": (ctypes.c_int32, [ctypes.POINTER(LsrRgbLossBwdArgs), _vp]),
+    "lsr_view_pack_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
+    "lsr_view_counts": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
+    "lsr_view_save": (ctypes.c_int32, [ctypes.POINTER(LsrViewArgs), _vp]),
+    "lsr_view_restore": (ctypes.c_int32, [ctypes.POINTER(LsrViewArgs), _vp]),
     "lsr_fill_language": (ctypes.c_int32, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_adam_step": (ctypes.c_int32, [ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_int64, _vp]),
@@ -680,6 +692,11 @@ def rasterize_gaussians(rs, means3D, shs, colors_precomp, language_feature, opac
                "lsr_forward")
     if cap is None:
         LAST_COUNTS[(P, W, H)] = (int(nr.value), int(entries.value))
+    elif a.phase == forward_phase.GEOMETRY and static_buffers.active() is not None:
+        # what a lsr_view_restore into this set needs to stand in for this call (view_restore_args)
+        static_buffers.active().geometry_call = dict(
+            P=P, W=W, H=H, flags=int(flags), rendered=cap.rendered, entries=cap.entries, overflow=cap.overflow,
+            fused_loss=int(out_loss is not None and bool(s.include_feature) and language_feature is not None))
     return (int(nr.value), color, lang, radii, alloc.get(LSR_BUF_GEOM), alloc.get(LSR_BUF_BINNING),
             alloc.get(LSR_BUF_IMAGE))
 
@@ -882,6 +899,52 @@ def fill_language(language_feature: torch.Tensor, raw: int, radii: torch.Tensor,
     with _on_device(lf.device):
         _check(load().lsr_fill_language(P, _ptr(lf), int(raw), _ptr(radii), ctypes.c_void_p(int(record_ptr)),
                                         _stream(lf.device)), "lsr_fill_language")
+
+
+def view_pack_bytes(P: int, W: int, H: int, num_rendered: int) -> int:
+    """Bytes of a view pack (include/lsr.h lsr_view_pack_bytes)."""
+    return int(load().lsr_view_pack_bytes(int(P), int(W), int(H), int(num_rendered)))
+
+
+def view_args(buffers: "static_buffers", num_rendered: int, pack: torch.Tensor) -> LsrViewArgs:
+    """lsr_view_args of one static_buffers set whose geometry-phase forward has run (its geometry_call
+    record: sizes, capacities, flags) and one pack tensor (uint8, at least view_pack_bytes)."""
+    call = buffers.geometry_call
+    a = LsrViewArgs()
+    a.P, a.width, a.height = call["P"], call["W"], call["H"]
+    a.flags, a.fused_loss = call["flags"], call["fused_loss"]
+    a.capacity_rendered, a.capacity_entries = call["rendered"], call["entries"]
+    a.num_rendered = int(num_rendered)
+    a.geom = buffers.tensors[("scratch", LSR_BUF_GEOM)].data_ptr()
+    a.image = buffers.tensors[("scratch", LSR_BUF_IMAGE)].data_ptr()
+    a.binning = buffers.tensors[("scratch", LSR_BUF_BINNING)].data_ptr()
+    a.radii = buffers.tensors[("out", "radii")].data_ptr()
+    a.pack = pack.data_ptr()
+    a.pack_bytes = int(pack.numel())
+    a.overflow = call["overflow"].data_ptr()
+    return a
+
+
+def view_counts(W: int, H: int, image: torch.Tensor, host: torch.Tensor, stream: "torch.cuda.Stream"):
+    """The set's eight counter slots (image: its LSR_BUF_IMAGE buffer) into `host`, a pinned int32 tensor
+    of 8, by a kernel on `stream` (include/lsr.h lsr_view_counts)."""
+    if not host.is_pinned() or host.dtype != torch.int32 or host.numel() < 8:
+        raise ValueError("view_counts: host must be a pinned int32 tensor of at least 8 elements")
+    with _on_device(stream.device):
+        _check(load().lsr_view_counts(int(W), int(H), _vp(image.data_ptr()), _vp(host.data_ptr()),
+                                      _vp(stream.cuda_stream)), "lsr_view_counts")
+
+
+def view_save(args: LsrViewArgs, stream: "torch.cuda.Stream"):
+    """The set's kept geometry into the pack, enqueued on `stream` (include/lsr.h lsr_view_save)."""
+    with _on_device(stream.device):
+        _check(load().lsr_view_save(ctypes.byref(args), _vp(stream.cuda_stream)), "lsr_view_save")
+
+
+def view_restore(args: LsrViewArgs, stream: "torch.cuda.Stream"):
+    """The pack back into the set in place of its geometry call, enqueued on `stream` (lsr_view_restore)."""
+    with _on_device(stream.device):
+        _check(load().lsr_view_restore(ctypes.byref(args), _vp(stream.cuda_stream)), "lsr_view_restore")
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

@@ -22,7 +22,7 @@ ROOT = os.path.dirname(HERE)
 BUILD_DIR = os.path.join(ROOT, "build", "lsr")
 LIB_PATH = os.path.join(HERE, "liblsr.so")
 SOURCES = ["lsr_preprocess.hip", "lsr_binning.hip", "lsr_render.hip", "lsr_loss.hip", "lsr_optim.hip", "lsr_knn.hip", "lsr_query.hip",
-           "lsr_eval.hip", "lsr_rgbloss.hip", "lsr_api.hip"]
+           "lsr_eval.hip", "lsr_rgbloss.hip", "lsr_viewcache.hip", "lsr_api.hip"]
 HEADERS = ["lsr_device.h", "lsr_internal.h"]
 # per-source extra flags: the render kernels write their packed (v_pk_*) arithmetic explicitly; the
 # SLP vectorizer would re-pack their scalar remainder across list entries at the cost of register

@@ -867,6 +867,78 @@ int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_allo
     return LSR_OK;
 }
 
+size_t lsr_view_pack_bytes(int32_t P, int32_t width, int32_t height, int64_t num_rendered)
+{
+    if (P < 1 || width < 1 || height < 1 || num_rendered < 0) return 0;
+    return make_view_pack(P, width, height, num_rendered).bytes;
+}
+
+int32_t lsr_view_counts(int32_t width, int32_t height, const void* image, uint32_t* host_counters, void* stream_ptr)
+{
+    if (width < 1 || height < 1 || !image || !host_counters ||
+        ((reinterpret_cast<uintptr_t>(image) | reinterpret_cast<uintptr_t>(host_counters)) & 3) != 0)
+        return fail(LSR_ERR_INVALID, "lsr_view_counts: a positive image size, the image buffer and 8 words of pinned "
+                                     "host memory are needed");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    const Layout L = make_layout(0, width, height, 0, 0);
+    LSR_TRY(launch_view_counts(reinterpret_cast<const uint32_t*>(static_cast<const char*>(image) + L.counters),
+                               host_counters, stream),
+            "view counts");
+    return LSR_OK;
+}
+
+static int32_t view_copy(const lsr_view_args* a, void* stream_ptr, bool restore)
+{
+    const char* who = restore ? "lsr_view_restore" : "lsr_view_save";
+    char msg[160];
+    auto bad = [&](const char* what) {
+        snprintf(msg, sizeof(msg), "%s: %s", who, what);
+        return fail(LSR_ERR_INVALID, msg);
+    };
+    if (!a) return bad("null argument");
+    if (a->P < 1 || a->width < 1 || a->height < 1 || a->width > 65535 * kTile || a->height > 65535 * kTile)
+        return bad("P, width and height must be positive");
+    if (a->capacity_rendered < 1 || a->capacity_entries < 1 || a->capacity_rendered > 0xFFFFFFFFll ||
+        a->capacity_entries > 0xFFFFFFFFll)
+        return bad("the capacities must be positive (both < 2^32)");
+    if (a->num_rendered < 0 || a->num_rendered > a->capacity_rendered)
+        return bad("num_rendered must be 0 .. capacity_rendered");
+    if (!a->geom || !a->image || !a->binning || !a->radii || !a->pack) return bad("null buffer");
+    if (a->pack_bytes < lsr_view_pack_bytes(a->P, a->width, a->height, a->num_rendered))
+        return bad("pack_bytes is below lsr_view_pack_bytes");
+    if (((reinterpret_cast<uintptr_t>(a->geom) | reinterpret_cast<uintptr_t>(a->image) |
+          reinterpret_cast<uintptr_t>(a->binning) | reinterpret_cast<uintptr_t>(a->pack)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(a->radii) & 3) != 0)
+        return bad("the buffers and the pack must be 16-byte aligned");
+    if (a->reserved != 0 || (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD)))
+        return bad("unknown flag");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    ViewParams v{};
+    v.P = a->P;
+    v.W = a->width;
+    v.H = a->height;
+    v.R_cap = a->capacity_rendered;
+    v.R = a->num_rendered;
+    v.geom = static_cast<char*>(a->geom);
+    v.image = static_cast<char*>(a->image);
+    v.binning = static_cast<char*>(a->binning);
+    v.pack = static_cast<char*>(a->pack);
+    v.radii = a->radii;
+    v.overflow = restore ? a->overflow : nullptr;
+    // counters[kCntFwdFlags] as forward_impl publishes it
+    v.fwd_flags = ((a->flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) |
+                  (a->fused_loss ? kFwdFusedLoss : 0u) | ((a->flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) |
+                  ((a->flags & LSR_FWD_NO_BACKWARD) ? kFwdNoBackward : 0u);
+    LSR_TRY(launch_view_copy(v, restore, stream), restore ? "view restore" : "view save");
+    return LSR_OK;
+}
+
+int32_t lsr_view_save(const lsr_view_args* a, void* stream) { return view_copy(a, stream, false); }
+
+int32_t lsr_view_restore(const lsr_view_args* a, void* stream) { return view_copy(a, stream, true); }
+
 int32_t lsr_profile_enable(int32_t on)
 {
     std::lock_guard<std::mutex> g(g_prof.mu);

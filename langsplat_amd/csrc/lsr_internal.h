@@ -486,6 +486,44 @@ hipError_t launch_query(QueryParams& p, hipStream_t s);
 hipError_t launch_eval_filter(const lsr_eval_filter_args& a, hipStream_t s);
 hipError_t launch_eval_masks(const lsr_eval_mask_args& a, hipStream_t s);
 
+// lsr_view_save / lsr_view_restore (lsr_viewcache.hip): byte offsets of a view pack's segments, each
+// 16-byte aligned (include/lsr.h lsr_view_pack_bytes documents the sizes)
+constexpr int kViewCounterWords = kCntSlots + kWorkClasses;  // the slots and the forward's class counts
+struct ViewPack {
+    size_t counters, rec01, recb, radii, clamped, ranges, order, point_list, bytes;
+};
+inline ViewPack make_view_pack(int P, int W, int H, int64_t R)
+{
+    ViewPack V{};
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o = align_up(o + bytes, 16); return r; };
+    const size_t p = (size_t)P, r = (size_t)R;
+    const size_t T = (size_t)((W + kTile - 1) / kTile) * (size_t)((H + kTile - 1) / kTile);
+    V.counters = take(4 * kViewCounterWords);
+    V.rec01 = take(32 * p);
+    V.recb = take(4 * p);
+    V.radii = take(4 * p);
+    V.clamped = take(4 * p);
+    V.ranges = take(8 * T);
+    V.order = take(4 * T);
+    V.point_list = take(4 * r);
+    V.bytes = o;
+    return V;
+}
+struct ViewParams {
+    int P, W, H;
+    int64_t R_cap, R;    // the set's capacity_rendered; the view's num_rendered
+    char *geom, *image, *binning, *pack;
+    int32_t* radii;
+    int32_t* overflow;   // restore: the caller's flag (0 afterwards), or null
+    uint32_t fwd_flags;  // restore: counters[kCntFwdFlags] as the geometry call would publish it
+};
+// one launch: the set's kept state into the pack, or (restore) back, with the words the geometry phase
+// clears on every run
+hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s);
+// counters[0..8) of an image buffer into pinned host memory (system-scope stores, as k_publish_counters)
+hipError_t launch_view_counts(const uint32_t* counters, uint32_t* host, hipStream_t s);
+
 hipError_t launch_render_forward(const RenderParams& p, int tiles, hipStream_t s);
 // lsr_forward_levels: the inference forward carrying 3 * levels language channels.  r is the
 // RenderParams of the single-level inference forward (no_bwd set; level 0 in the records and in

@@ -1,0 +1,210 @@
+// lsr_viewcache.hip -- lsr_view_save / lsr_view_restore: a view's frozen geometry as one compact pack.
+//
+// In LangSplat's language stage every geometry parameter is frozen (scene/gaussian_model.py:203-217),
+// so what LSR_PHASE_GEOMETRY (preprocess, depth order, binning) leaves for a given camera is the same
+// at every step.  k_view_copy<false> gathers the part of it the later phases read -- the composite
+// phase, lsr_backward (language step and all-gradients step) and lsr_language_tail -- into a pack;
+// k_view_copy<true> scatters a pack back into a buffer set of the same capacities and re-initialises
+// the words the geometry phase clears on every run.  One launch each, grid-stride over the segments,
+// consecutive lanes on consecutive 16-byte words; no LDS.
+//
+// What is kept (make_view_pack), read off render_forward_and_finish, lsr_backward's parameter setup and
+// make_layout:
+//   counters   the published slots (tile instances, error, super-tile entries, key range) and the
+//              forward's class counts of the longest-first schedule (k_bin_emit's)
+//   rec01      record[3 i], record[3 i + 1]: position, conic, opacity, r, g
+//   recb       word 0 of record[3 i + 2]: b.  Its other three words are the language slots, which
+//              belong to the feature fill (a fused update may write them before, while or after a
+//              restore runs, as with the geometry call): never read, never written here
+//   radii, clamped (the all-gradients backward's preprocess backward reads clamped)
+//   ranges     the tiles' [start, end) in the point list
+//   order      the forward's class lists, compacted: the scheduled tiles class by class, ascending
+//              class, each class in its list's order (workgroup b's tile, and with it the order in
+//              which the fused loss adds the workgroups' shares, is what it was)
+//   point_list the num_rendered entries
+// Not kept: depth keys, sort and scan scratch, super-tile tables (geometry-internal); cover bytes,
+// split states, the backward's class counts and lists, final_T, n_contrib, loss codes (the compositing
+// writes them); the language slots; the gradient records (cleared by the compositing or the backward).
+#include "lsr_internal.h"
+
+namespace lsr {
+
+namespace {
+
+constexpr int kViewThreads = 256;
+// the guides' cap for memory-bound grids on this chip (256 CUs x 8 blocks), grid-stride beyond
+constexpr int kViewMaxBlocks = 2048;
+
+enum ViewSeg : int { kSegRecord, kSegPointList, kSegRadii, kSegClamped, kSegRanges, kSegOrder, kSegCounters, kSegLoss, kSegs };
+
+struct ViewCopy {
+    size_t end[kSegs];  // running ends of the segments' item ranges
+    int P, T;
+    int64_t R;
+    int radii_vec;      // radii is 16-byte aligned
+    uint32_t fwd_flags; // restore: counters[kCntFwdFlags]
+    float4* record;
+    int32_t* radii;
+    uint4* clamped;
+    uint4* ranges;
+    uint32_t* lists;
+    uint4* point_list;
+    uint32_t* counters;
+    uint4* loss_words;
+    int32_t* overflow;
+    uint32_t* pk_counters;
+    float4* pk_rec01;
+    float* pk_recb;
+    int32_t* pk_radii;
+    uint4* pk_clamped;
+    uint4* pk_ranges;
+    uint32_t* pk_order;
+    uint4* pk_point_list;
+};
+
+template <bool kRestore, typename T>
+__device__ __forceinline__ void move(T* set, T* pack, size_t i)
+{
+    if (kRestore)
+        set[i] = pack[i];
+    else
+        pack[i] = set[i];
+}
+
+template <bool kRestore>
+__global__ __launch_bounds__(kViewThreads) void k_view_copy(ViewCopy p)
+{
+    const size_t stride = (size_t)gridDim.x * kViewThreads;
+    for (size_t i = (size_t)blockIdx.x * kViewThreads + threadIdx.x; i < p.end[kSegs - 1]; i += stride) {
+        if (i < p.end[kSegRecord]) {
+            // float4 k of the record array: Gaussian g = k / 3, word w = k % 3
+            const size_t g = i / 3;
+            const int w = (int)(i - 3 * g);
+            if (w < 2) {
+                if (kRestore)
+                    p.record[i] = p.pk_rec01[i - g];
+                else
+                    p.pk_rec01[i - g] = p.record[i];
+            } else {  // b only: the language slots stay as they are
+                float* b = reinterpret_cast<float*>(p.record + i);
+                if (kRestore)
+                    *b = p.pk_recb[g];
+                else
+                    p.pk_recb[g] = *b;
+            }
+        } else if (i < p.end[kSegPointList]) {
+            // (both arrays are padded past 4 ceil(R / 4) entries)
+            move<kRestore>(p.point_list, p.pk_point_list, i - p.end[kSegRecord]);
+        } else if (i < p.end[kSegRadii]) {
+            const size_t q = i - p.end[kSegPointList];
+            if (p.radii_vec && 4 * q + 4 <= (size_t)p.P) {
+                move<kRestore>(reinterpret_cast<int4*>(p.radii), reinterpret_cast<int4*>(p.pk_radii), q);
+            } else {  // the caller's array ends at P and may sit at any 4-byte address
+                for (size_t j = 4 * q; j < 4 * q + 4 && j < (size_t)p.P; j++) move<kRestore>(p.radii, p.pk_radii, j);
+            }
+        } else if (i < p.end[kSegClamped]) {
+            move<kRestore>(p.clamped, p.pk_clamped, i - p.end[kSegRadii]);
+        } else if (i < p.end[kSegRanges]) {
+            move<kRestore>(p.ranges, p.pk_ranges, i - p.end[kSegClamped]);
+        } else if (i < p.end[kSegOrder]) {
+            // scheduled slot j: its class from the class counts (the pack's when restoring: the set's
+            // are written by this launch), then the list element
+            const uint32_t j = (uint32_t)(i - p.end[kSegRanges]);
+            const uint32_t* cnt = (kRestore ? p.pk_counters : p.counters) + kCntFwdClass;
+            uint32_t first = 0;
+            for (int c = 0; c < kWorkClasses; c++) {
+                const uint32_t n = min(cnt[c], (uint32_t)p.T);
+                if (j - first < n) {
+                    uint32_t* slot = p.lists + (size_t)c * p.T + (j - first);
+                    if (kRestore)
+                        *slot = p.pk_order[j];
+                    else
+                        p.pk_order[j] = *slot;
+                    break;
+                }
+                first += n;  // (j >= first still holds)
+            }
+        } else if (i < p.end[kSegCounters]) {
+            const int c = (int)(i - p.end[kSegOrder]);
+            if (!kRestore) {
+                p.pk_counters[c] = p.counters[c];
+            } else {
+                // as k_publish_counters leaves them: the five published values, the forward's flags, the
+                // forward's class counts; every other word 0 (the overflow word, the backward's class
+                // counts that the compositing adds to)
+                uint32_t v = 0u;
+                if (c == kCntRendered || c == kCntError || c == kCntSuper || c == kCntKeyMin || c == kCntKeyMax ||
+                    (c >= kCntFwdClass && c < kCntBwdClass))
+                    v = p.pk_counters[c];
+                else if (c == kCntFwdFlags)
+                    v = p.fwd_flags;
+                p.counters[c] = v;
+                if (c == kCntOverflow && p.overflow) *p.overflow = 0;
+            }
+        } else {  // restore: the fused loss's words start at 0 (the preprocess clears them)
+            p.loss_words[i - p.end[kSegCounters]] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_view_counts(const uint32_t* __restrict__ counters, uint32_t* host)
+{
+    if (threadIdx.x < 8)
+        __hip_atomic_store(&host[threadIdx.x], counters[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+}  // namespace
+
+hipError_t launch_view_counts(const uint32_t* counters, uint32_t* host, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_view_counts, dim3(1), dim3(64), 0, s, counters, host);
+    return hipGetLastError();
+}
+
+hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s)
+{
+    const Layout L = make_layout(v.P, v.W, v.H, v.R_cap, 0);  // point_list sits at offset 0
+    const ViewPack V = make_view_pack(v.P, v.W, v.H, v.R);
+    ViewCopy p{};
+    p.P = v.P;
+    p.T = L.tiles;
+    p.R = v.R;
+    p.radii_vec = (reinterpret_cast<uintptr_t>(v.radii) & 15) == 0 ? 1 : 0;
+    p.fwd_flags = v.fwd_flags;
+    p.record = reinterpret_cast<float4*>(v.geom + L.record);
+    p.radii = v.radii;
+    p.clamped = reinterpret_cast<uint4*>(v.geom + L.clamped);
+    p.ranges = reinterpret_cast<uint4*>(v.image + L.ranges);
+    p.lists = reinterpret_cast<uint32_t*>(v.image + L.tile_lists);
+    p.point_list = reinterpret_cast<uint4*>(v.binning + L.point_list);
+    p.counters = reinterpret_cast<uint32_t*>(v.image + L.counters);
+    p.loss_words = reinterpret_cast<uint4*>(v.geom + L.loss_words);
+    p.overflow = v.overflow;
+    p.pk_counters = reinterpret_cast<uint32_t*>(v.pack + V.counters);
+    p.pk_rec01 = reinterpret_cast<float4*>(v.pack + V.rec01);
+    p.pk_recb = reinterpret_cast<float*>(v.pack + V.recb);
+    p.pk_radii = reinterpret_cast<int32_t*>(v.pack + V.radii);
+    p.pk_clamped = reinterpret_cast<uint4*>(v.pack + V.clamped);
+    p.pk_ranges = reinterpret_cast<uint4*>(v.pack + V.ranges);
+    p.pk_order = reinterpret_cast<uint32_t*>(v.pack + V.order);
+    p.pk_point_list = reinterpret_cast<uint4*>(v.pack + V.point_list);
+    const size_t P = (size_t)v.P, T = (size_t)L.tiles, R = (size_t)v.R;
+    size_t n = 0;
+    p.end[kSegRecord] = n += 3 * P;
+    p.end[kSegPointList] = n += (R + 3) / 4;
+    p.end[kSegRadii] = n += (P + 3) / 4;
+    p.end[kSegClamped] = n += (P + 3) / 4;
+    p.end[kSegRanges] = n += (T + 1) / 2;
+    p.end[kSegOrder] = n += T;
+    p.end[kSegCounters] = n += restore ? (size_t)kCntWords : (size_t)kViewCounterWords;
+    p.end[kSegLoss] = n += restore ? (T + 1) / 2 : 0;
+    const size_t blocks = (n + kViewThreads - 1) / kViewThreads;
+    const dim3 grid((unsigned)(blocks < (size_t)kViewMaxBlocks ? blocks : (size_t)kViewMaxBlocks));
+    if (restore)
+        hipLaunchKernelGGL(k_view_copy<true>, grid, dim3(kViewThreads), 0, s, p);
+    else
+        hipLaunchKernelGGL(k_view_copy<false>, grid, dim3(kViewThreads), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace lsr

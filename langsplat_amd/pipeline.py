@@ -97,6 +97,115 @@ class ViewPipeline:
             cur.wait_stream(s)
 
 
+class ViewCache:
+    """The bookkeeping of PipelinedGraphStep's view cache: which views have a pack (include/lsr.h
+    lsr_view_save), which buffer sets hold a geometry result that could still be saved, the byte
+    budget and the parameter stamp the packs were made under.  It enqueues nothing itself: `native`
+    does (PipelinedGraphStep's _ViewNative, or a stand-in in tests), with
+
+        native.pack_bytes(num_rendered) -> int         bytes of a pack of that many tile instances
+        native.alloc(nbytes) -> pack                   device memory for one pack
+        native.save(r, num_rendered, pack)             set r's geometry into the pack (stream B)
+        native.restore(r, num_rendered, pack)          the pack into set r (stream B)
+
+    A view's key is any hashable; `ref` is kept with it (the camera object: its id stays unique while
+    the cache holds it).  There is no eviction: an epoch is a permutation of the views, so LRU would
+    miss every time; once the budget is full the remaining views keep running their geometry graph."""
+
+    RENDERED, OVERFLOW = 1, 7  # counter slots (csrc/lsr_internal.h kCntRendered, kCntOverflow)
+
+    def __init__(self, sets: int, budget_bytes: int, native):
+        self.native = native
+        self.budget = int(budget_bytes)
+        self.packs = {}                 # key -> (ref, num_rendered, pack, nbytes)
+        self.pending = [None] * sets    # per set: (key, ref, event, host counters) of a geometry graph's result
+        self.stamp = None
+        self.bytes = self.hits = self.misses = self.drops = 0
+
+    def invalidate(self):
+        """Drop every pack, and every set's claim to hold a result worth saving."""
+        if self.packs:
+            self.drops += 1
+        self.packs.clear()
+        self.pending = [None] * len(self.pending)
+        self.bytes = 0
+
+    def check(self, stamp):
+        """The geometry tensors' (data_ptr, _version) stamp at this replay: another one than the packs
+        were made under drops them (and what the sets hold was computed before the change)."""
+        if stamp != self.stamp:
+            if self.stamp is not None:
+                self.invalidate()
+            self.stamp = stamp
+
+    def computed(self, r, key, ref, event, host):
+        """Set r's geometry graph was just enqueued for view `key`; `event` follows the copy of its
+        counter slots into `host` (pinned).  Nothing is pending for a view that has a pack."""
+        self.pending[r] = None if key in self.packs else (key, ref, event, host)
+
+    def visit(self, r, key) -> bool:
+        """Set r is about to receive view `key` (its last reader is done, on stream B's order).  First
+        the view it holds is saved, if its counters have arrived (no wait: an event not yet signalled
+        skips this visit), it fitted its capacities and the budget allows.  True: `key` has a pack and
+        its restore was enqueued in place of the geometry graph."""
+        pend, self.pending[r] = self.pending[r], None
+        if pend is not None and pend[0] not in self.packs and pend[2].query():
+            pkey, ref, _, host = pend
+            if int(host[self.OVERFLOW]) == 0:
+                rendered = int(host[self.RENDERED])
+                nbytes = self.native.pack_bytes(rendered)
+                if self.bytes + nbytes <= self.budget:
+                    pack = self.native.alloc(nbytes)
+                    self.native.save(r, rendered, pack)
+                    self.packs[pkey] = (ref, rendered, pack, nbytes)
+                    self.bytes += nbytes
+        hit = self.packs.get(key)
+        if hit is None:
+            self.misses += 1
+            return False
+        self.native.restore(r, hit[1], hit[2])
+        self.hits += 1
+        return True
+
+    def stats(self):
+        return {"hits": self.hits, "misses": self.misses, "packs": len(self.packs), "bytes": self.bytes,
+                "drops": self.drops}
+
+
+class _ViewNative:
+    """ViewCache's device side for one PipelinedGraphStep: packs are uint8 tensors, save and restore go
+    to stream B with each (set, pack)'s lsr_view_args built once.  It holds the step's buffer sets and
+    stream, not the step: no reference cycle, so a step's graphs and packs are freed when its last
+    reference goes (not by a later garbage collection, which could run inside a graph capture)."""
+
+    def __init__(self, sets, stream, device):
+        self.sets, self.stream, self.device = sets, stream, device
+        self.args = {}  # (set, pack address and size, tile instances) -> LsrViewArgs
+        call = sets[0].geometry_call
+        self.dims = (call["P"], call["W"], call["H"])
+
+    def pack_bytes(self, rendered):
+        return _native.view_pack_bytes(*self.dims, rendered)
+
+    def alloc(self, nbytes):
+        pack = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
+        pack.record_stream(self.stream)  # used on stream B only, whatever stream allocates it
+        return pack
+
+    def _args(self, r, rendered, pack):
+        key = (r, pack.data_ptr(), pack.numel(), rendered)
+        a = self.args.get(key)
+        if a is None:
+            a = self.args[key] = _native.view_args(self.sets[r], rendered, pack)
+        return a
+
+    def save(self, r, rendered, pack):
+        _native.view_save(self._args(r, rendered, pack), self.stream)
+
+    def restore(self, r, rendered, pack):
+        _native.view_restore(self._args(r, rendered, pack), self.stream)
+
+
 class PipelinedGraphStep:
     """ViewPipeline's order as HIP graphs on two streams: the geometry stages of a later view run on
     stream B while view k's compositing, loss, backward and Adam run on stream A, with no host work
@@ -158,6 +267,21 @@ class PipelinedGraphStep:
     queue each at C3) and the following R views' geometry on stream B; the replays in between launch
     nothing.  Parameters, learning rates and check() apply at rotation boundaries (k % R == 0).
 
+    View cache (view_cache=True, N >= 1, rotation == 1): the language stage freezes every geometry
+    parameter, and an epoch visits every view again, so a view's geometry half gives the same result at
+    every visit.  When `model` is passed and none of its _xyz, _scaling, _rotation, _opacity,
+    _features_dc, _features_rest requires grad, the first visit of a view runs G_geo as before; when its
+    set is next about to receive a view, what the later phases read of that result is saved into a
+    pack (lsr_view_save; ~74 MB at 1M Gaussians and 1080p), and every later visit enqueues ONE copy
+    kernel (lsr_view_restore) on stream B in place of G_geo -- same waits before it, same event after
+    it, the captured graphs untouched.  Views are keyed by their camera object (slots; the cache holds
+    a reference), or by one constant key for the fixed view without slots, which therefore pays a
+    restore per replay like any revisit.  view_cache_bytes bounds the packs (None: half of the device
+    memory free at capture); there is no eviction.  Every pack is dropped at a (re-)capture, when any of
+    the six tensors' (data_ptr(), _version) changes between replays, and by invalidate_views() -- call
+    it after changing a camera object's tensors in place.  Rotation mode keeps its geometry graphs (no
+    cache).  view_cache_stats() counts hits, misses, packs and bytes.
+
     Knobs: the `sets` argument (default 3), LSR_PG_ROT (the `rotation` argument's default),
     LSR_PG_DEFER=0 (N > 1: the gradient epilogue stays in the backward) and LSR_PG_NATIVE_LAUNCH=0
     (every replay through torch's stream context).  Forms measured at C3 and not kept (DESIGN.md
@@ -165,7 +289,8 @@ class PipelinedGraphStep:
     and the step as two graphs, a host throttle on the replays enqueued ahead."""
 
     def __init__(self, forward_fn, params, optimizer, headroom: float = 1.125, warmup: int = 2, bucket=None,
-                 slots=None, sets: int = None, rotation: int = None, model=None, bucket_factory=None):
+                 slots=None, sets: int = None, rotation: int = None, model=None, bucket_factory=None,
+                 view_cache: bool = True, view_cache_bytes: int = None):
         self.forward_fn = forward_fn
         self.model = model  # its active_sh_degree is part of the capture key (graph.capture_key)
         self.params = [p for p in params]
@@ -207,6 +332,9 @@ class PipelinedGraphStep:
         self._tails = [None] * self.S
         self._loaded = [None] * S  # the view each set's slot holds (slots only)
         self._assigned = [None] * S  # rotation mode: the view each set's next geometry renders
+        self.view_cache = bool(view_cache)
+        self.view_cache_bytes = view_cache_bytes
+        self._views = None  # the ViewCache while it is active (set by capture)
 
     def _reset_graphs(self):
         S = self.S
@@ -246,6 +374,7 @@ class PipelinedGraphStep:
         """views: the first S - 1 views (camera, gt, mask) when the step renders from ViewSlots (a
         shorter list repeats its last view); the capacities are measured on them."""
         S = self.S
+        self._views = None  # every pack goes before anything is measured or captured
         if self.slots is not None:
             if not views:
                 raise ValueError("PipelinedGraphStep.capture: the first views are needed with slots")
@@ -390,7 +519,55 @@ class PipelinedGraphStep:
         self._launchers = {}  # (set, fast) -> _native.GraphLauncher (replay's steady state)
         self._refill = fill_after  # the first composite's records: from the parameter (replay)
         self.captures += 1
+        self._views = self._make_view_cache()  # (a re-capture starts empty: the layouts changed)
         return self
+
+    _GEOMETRY_TENSORS = ("_xyz", "_scaling", "_rotation", "_opacity", "_features_dc", "_features_rest")
+
+    def _geometry_tensors(self):
+        """The model's six geometry tensors when every one of them is frozen, else None."""
+        ts = [getattr(self.model, n, None) for n in self._GEOMETRY_TENSORS]
+        if any(not torch.is_tensor(t) or t.requires_grad for t in ts):
+            return None
+        return ts
+
+    def _make_view_cache(self):
+        if not self.view_cache or self.model is None or self.R != 1 or self._geometry_tensors() is None:
+            return None
+        call = getattr(self.sets[0], "geometry_call", None)
+        if call is None or call["P"] < 1:
+            return None
+        budget = self.view_cache_bytes
+        if budget is None:
+            budget = torch.cuda.mem_get_info(self.params[0].device)[0] // 2
+        if budget <= 0:
+            return None
+        # per set: its image buffer (the counter slots) and the pinned words a kernel copies them to
+        self._cnt_size = (call["W"], call["H"])
+        self._cnt_dev = [st.tensors[("scratch", _native.LSR_BUF_IMAGE)] for st in self.sets]
+        self._cnt_host = [torch.zeros((8,), dtype=torch.int32).pin_memory() for _ in self.sets]
+        return ViewCache(self.S, budget, _ViewNative(self.sets, self.streams[1], self.params[0].device))
+
+    def _view_key(self, r):
+        """(key, reference) of the view set r's geometry renders: its camera object, or the fixed view."""
+        if self.slots is None:
+            return 0, None
+        if self._loaded[r] is None:  # no view loaded yet: whatever the set's slot was built with
+            return ("slot", r), None
+        cam = _as_view(self._loaded[r])[0]
+        return id(cam), cam
+
+    def invalidate_views(self):
+        """Drop every cached view (e.g. after changing a camera's tensors in place)."""
+        if self._views is not None:
+            self._views.invalidate()
+
+    def view_cache_stats(self):
+        """{"hits", "misses", "packs", "bytes", "drops"} of the view cache since the last capture: restores,
+        geometry graphs run, packs held and their bytes, invalidations (zeros while it is inactive)."""
+        if self._views is None:
+            return {"hits": 0, "misses": 0, "packs": 0, "bytes": 0, "drops": 0}
+        return self._views.stats()
 
     def _capture_rotations(self, caps, comp_phase, fused, step_body):
         """Rotation mode: per group j of R sets (j = 0: sets 0..R-1, j = 1: sets R..2R-1) one graph
@@ -510,8 +687,21 @@ class PipelinedGraphStep:
             sb.wait_event(released)
         else:
             sb.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(sb):
-            self.g_geo[r].replay()
+        vc = self._views
+        if vc is None:
+            with torch.cuda.stream(sb):
+                self.g_geo[r].replay()
+        else:
+            key, ref = self._view_key(r)
+            if not vc.visit(r, key):  # (a hit enqueued the view's restore instead)
+                with torch.cuda.stream(sb):
+                    self.g_geo[r].replay()
+                # the view's counts and overflow word to the host, for a save when the set is next
+                # released: a one-wave kernel before the set's own event.  (Stream B is a first epoch's
+                # critical path: a device-to-host copy with an event of its own there measured +0.05 ms
+                # per step, the same copy on a third stream +0.07, profiles/view_cache_ab.txt.)
+                _native.view_counts(*self._cnt_size, self._cnt_dev[r], self._cnt_host[r], sb)
+                vc.computed(r, key, ref, self.ev_geo[r], self._cnt_host[r])
         self.ev_geo[r].record(sb)
 
     def _launcher(self, p, fast):
@@ -551,6 +741,12 @@ class PipelinedGraphStep:
             self._recapture(self.rendered, self.entries)
         if self.R > 1:
             return self._replay_rotation(next_view, wait)
+        if self._views is not None:
+            ts = self._geometry_tensors()
+            if ts is None:  # a geometry tensor became trainable: no cache until the next capture
+                self._views = None
+            else:
+                self._views.check(tuple((t.data_ptr(), t._version) for t in ts))
         S = self.S
         sa, sb = self.streams
         p = self.k % S
