@@ -704,6 +704,62 @@ int32_t lsr_forward_levels(const lsr_settings* settings, const lsr_forward_level
  * its registers and LDS with the hardware's allocation granules; negative (-lsr_status) on error. */
 int32_t lsr_debug_levels_occupancy(int32_t levels);
 
+/* ---- the language gradient of all levels in one pass (the backward of lsr_forward_levels) ---------
+ * With the geometry frozen the levels' only gradient is the one of their language features, and for
+ * the activated features a it is
+ *     dL/da[l][k][c] = sum over pixels of w_k(pixel) * g[l][c](pixel),     w_k = alpha_k T_k,
+ * with w the forward's own blend weight and g = dL/d(level l's map).  T_k is the forward's running
+ * product, so lsr_backward_levels accumulates the sums front to back by running the forward's walk a
+ * second time; it reads only what the inference forward leaves in its three buffers (the records,
+ * the tile ranges, the point list and the longest-first tile lists).  lsr_backward still must NOT
+ * follow lsr_forward_levels (no backward state was written): this call is the only backward of that
+ * forward.  The buffers must be those of a lsr_forward_levels call with the same settings, P and
+ * geometry (levels == 1: lsr_forward_levels with levels == 1, i.e. lsr_forward under
+ * LSR_FWD_NO_BACKWARD), unchanged since, and num_rendered the value it returned.
+ *
+ * The seed g is dL_dout_language_feature, the fused masked-L1 seed, or their sum when both are given.
+ * The fused seed is the gradient of  sum_l dL_dloss[l] * l1_loss(map_l * mask_l, target_l * mask_l):
+ *     g[l][c] = dL_dloss[l] * sign(f m - gt m) * m / (3 H W)
+ * (lsr_backward_args.dL_dloss's expression), formed per pixel from out_language_feature (the forward's
+ * maps), loss_target and loss_mask, so no levels x 3 x H x W gradient image is materialised.  Its
+ * four pointers are all set or all NULL.
+ *
+ * Every entry of dL_dlanguage_feature is written: the gradient w.r.t. language_feature when raw has
+ * LSR_RAW_LANGUAGE (the normalisation's chain rule per level; language_feature is read only then),
+ * else w.r.t. the activated features; exact zeros for culled Gaussians (radii <= 0).  With P == 0
+ * nothing is written; with num_rendered == 0 or all-zero seeds the output is zeros.  `scratch` is
+ * lsr_backward_levels_bytes(P, levels) bytes (P rows of 3 levels floats; 0 for P <= 0 or levels outside
+ * 1..LSR_MAX_LEVELS), cleared by the call itself.  The call enqueues its work on `stream` and never
+ * waits for the device.  The sums are float atomic adds: the last bits depend on arrival order.
+ *
+ * Refused with LSR_ERR_INVALID before any device work, the message naming the field: a NULL settings
+ * or args; levels outside 1..LSR_MAX_LEVELS; reserved != 0; P < 0; num_rendered < 0;
+ * settings.include_feature == 0; with P > 0 a NULL geom_buffer, binning_buffer, image_buffer, radii,
+ * scratch or dL_dlanguage_feature; raw & LSR_RAW_LANGUAGE with a NULL language_feature (P > 0); a
+ * partial set of out_language_feature, loss_target, loss_mask and dL_dloss; neither seed given.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+typedef struct lsr_backward_levels_args {
+    int32_t P;
+    int32_t levels;                         /* 1 .. LSR_MAX_LEVELS */
+    int32_t raw;                            /* lsr_raw_flags; only LSR_RAW_LANGUAGE is read */
+    int32_t reserved;                       /* 0 */
+    int64_t num_rendered;                   /* value returned by lsr_forward_levels */
+    void* geom_buffer;                      /* the forward's three buffers */
+    void* binning_buffer;
+    void* image_buffer;
+    const int32_t* radii;                   /* P, the forward's */
+    const float* language_feature;          /* levels x P x 3, level-major; read iff raw & LSR_RAW_LANGUAGE */
+    const float* dL_dout_language_feature;  /* levels x 3 x H x W, or NULL */
+    const float* out_language_feature;      /* fused seed: the forward's maps, levels x 3 x H x W, or NULL */
+    const float* loss_target;               /* fused seed: levels x 3 x H x W, or NULL */
+    const uint8_t* loss_mask;               /* fused seed: levels x H x W bool bytes, or NULL */
+    const float* dL_dloss;                  /* fused seed: levels device floats, or NULL */
+    void* scratch;                          /* lsr_backward_levels_bytes(P, levels) bytes */
+    float* dL_dlanguage_feature;            /* levels x P x 3 */
+} lsr_backward_levels_args;
+size_t lsr_backward_levels_bytes(int32_t P, int32_t levels);
+int32_t lsr_backward_levels(const lsr_settings* settings, const lsr_backward_levels_args* args, void* stream);
+
 /* ---- a view's frozen geometry, kept across steps of the language stage ---------------------------
  * In the language stage every geometry parameter is frozen (scene/gaussian_model.py:203-217), and
  * train.py:85-87 draws each of a scene's views again every epoch: for one camera, what a

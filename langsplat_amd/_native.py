@@ -67,6 +67,14 @@ class LsrForwardLevelsArgs(ctypes.Structure):
                 ("more_language_feature", _vp), ("more_out_language_feature", _vp)]
 
 
+class LsrBackwardLevelsArgs(ctypes.Structure):
+    _fields_ = [("P", ctypes.c_int32), ("levels", ctypes.c_int32), ("raw", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("num_rendered", ctypes.c_int64)] + [
+        (n, _vp) for n in ("geom_buffer", "binning_buffer", "image_buffer", "radii", "language_feature",
+                           "dL_dout_language_feature", "out_language_feature", "loss_target", "loss_mask",
+                           "dL_dloss", "scratch", "dL_dlanguage_feature")]
+
+
 class LsrAdamTensor(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int64), ("param", _vp), ("grad", _vp), ("exp_avg", _vp), ("exp_avg_sq", _vp),
                 ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double),
@@ -161,6 +169,8 @@ SIGNATURES = {
     "lsr_debug_levels_occupancy": (ctypes.c_int32, [ctypes.c_int32]),
     "lsr_forward_levels": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrForwardLevelsArgs),
                                             ALLOC_FN, _vp, _vp, ctypes.POINTER(ctypes.c_int64)]),
+    "lsr_backward_levels_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
+    "lsr_backward_levels": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrBackwardLevelsArgs), _vp]),
     "lsr_mark_visible": (ctypes.c_int32, [ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "lsr_query_relevancy": (ctypes.c_int32, [ctypes.POINTER(LsrQueryArgs), _vp]),
     "lsr_eval_filter": (ctypes.c_int32, [ctypes.POINTER(LsrEvalFilterArgs), _vp]),
@@ -713,12 +723,14 @@ def check_level_features(language_features, P: int) -> int:
 
 
 def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_features, opacities, scales, rotations,
-                               cov3D_precomp, raw=0, shs_rest=None, with_visibility=False):
+                               cov3D_precomp, raw=0, shs_rest=None, with_visibility=False, keep_state=False):
     """All language levels of a scene in one inference forward (include/lsr.h lsr_forward_levels):
     language_features is (L, P, 3), 1 <= L <= MAX_LEVELS, raw iff raw has RAW_LANGUAGE; the other
     arguments are rasterize_gaussians'.  Returns (num_rendered, color (3, H, W), language_images
     (L, 3, H, W), radii), and with_visibility the (P,) bool radii > 0 after them.  Level l's image is
-    bit-identical to rasterize_gaussians' for language_features[l]; nothing is kept for a backward."""
+    bit-identical to rasterize_gaussians' for language_features[l].  keep_state: the forward's geometry,
+    binning and image buffers after everything else, for rasterize_gaussians_levels_backward (the only
+    backward of this forward); otherwise nothing is kept."""
     lib = load()
     device = means3D.device
     P = int(means3D.shape[0])
@@ -744,7 +756,59 @@ def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_featur
         _check(lib.lsr_forward_levels(ctypes.byref(s), ctypes.byref(la), _ALLOC_CB, None, _stream(device),
                                       ctypes.byref(nr)), "lsr_forward_levels")
     out = (int(nr.value), color, langs, radii)
-    return out + (visible,) if with_visibility else out
+    if with_visibility:
+        out += (visible,)
+    if keep_state:
+        out += (alloc.get(LSR_BUF_GEOM), alloc.get(LSR_BUF_BINNING), alloc.get(LSR_BUF_IMAGE))
+    return out
+
+
+def rasterize_gaussians_levels_backward(rs, language_features, radii, num_rendered, geom, binning, image, raw=0,
+                                        grad_images=None, images=None, targets=None, masks=None, grad_losses=None):
+    """The language gradient of every level of a rasterize_gaussians_levels(..., keep_state=True) forward
+    (include/lsr.h lsr_backward_levels): (L, P, 3), w.r.t. language_features (raw iff raw has
+    RAW_LANGUAGE), zeros for culled Gaussians.  Seeds: grad_images (L, 3, H, W) = dL/d(the maps), and /
+    or the fused masked-L1 seed of sum_l grad_losses[l] * l1_loss(images[l] * masks[l], targets[l] *
+    masks[l]): images (the forward's maps) and targets (L, 3, H, W), masks (L, H, W) bool, grad_losses
+    (L,), all four or none.  Both given: their sum."""
+    lib = load()
+    device = radii.device
+    P = int(radii.shape[0])
+    L = check_level_features(language_features, P)
+    H, W = int(rs.image_height), int(rs.image_width)
+    keep: list = []
+    s = make_settings(rs, keep)
+    fused = [images, targets, masks, grad_losses]
+    if any(x is not None for x in fused) and any(x is None for x in fused):
+        raise ValueError("rasterize_gaussians_levels_backward: images, targets, masks and grad_losses go together")
+    if grad_images is None and images is None:
+        raise ValueError("rasterize_gaussians_levels_backward: no seed (grad_images or the fused seed)")
+    a = LsrBackwardLevelsArgs()
+    a.P, a.levels, a.raw, a.num_rendered = P, L, int(raw) & RAW_LANGUAGE, int(num_rendered)
+    lf = _f32c(language_features.detach())
+    a.language_feature = _ptr(lf)
+    for name, t in (("grad_images", grad_images), ("images", images), ("targets", targets)):
+        if t is not None and tuple(t.shape) != (L, 3, H, W):
+            raise ValueError(f"rasterize_gaussians_levels_backward: {name} must be ({L}, 3, {H}, {W}), got "
+                             f"{tuple(t.shape)}")
+    if grad_images is not None:
+        keep.append(_f32c(grad_images.detach()))
+        a.dL_dout_language_feature = keep[-1].data_ptr()
+    if images is not None:
+        if masks.dtype != torch.bool or tuple(masks.shape) != (L, H, W) or tuple(grad_losses.shape) != (L,):
+            raise ValueError(f"rasterize_gaussians_levels_backward: masks must be ({L}, {H}, {W}) bool and "
+                             f"grad_losses ({L},)")
+        keep += [_f32c(images.detach()), _f32c(targets.detach()), masks.contiguous(), _f32c(grad_losses.detach())]
+        a.out_language_feature, a.loss_target, a.loss_mask, a.dL_dloss = (t.data_ptr() for t in keep[-4:])
+    out = torch.empty((L, P, 3), dtype=torch.float32, device=device)
+    scratch = torch.empty((int(lib.lsr_backward_levels_bytes(P, L)),), dtype=torch.uint8, device=device)
+    a.geom_buffer, a.binning_buffer, a.image_buffer = _ptr(geom), _ptr(binning), _ptr(image)
+    a.radii = _ptr(radii)
+    a.scratch = _ptr(scratch)
+    a.dL_dlanguage_feature = _ptr(out)
+    with _on_device(device):
+        _check(lib.lsr_backward_levels(ctypes.byref(s), ctypes.byref(a), _stream(device)), "lsr_backward_levels")
+    return out
 
 
 # LSR_ALL_GRADS=1 (or setting this to True) computes every geometry gradient even when no input

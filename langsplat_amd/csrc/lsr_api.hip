@@ -686,6 +686,80 @@ int32_t lsr_forward_levels(const lsr_settings* s, const lsr_forward_levels_args*
     return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, &lv);
 }
 
+size_t lsr_backward_levels_bytes(int32_t P, int32_t levels)
+{
+    if (P <= 0 || levels < 1 || levels > LSR_MAX_LEVELS) return 0;
+    return align_up(sizeof(float) * 3 * (size_t)levels * (size_t)P);
+}
+
+int32_t lsr_backward_levels(const lsr_settings* s, const lsr_backward_levels_args* a, void* stream_ptr)
+{
+    if (!s) return fail(LSR_ERR_INVALID, "lsr_backward_levels: settings is NULL");
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_backward_levels: args is NULL");
+    if (a->levels < 1 || a->levels > LSR_MAX_LEVELS)
+        return fail(LSR_ERR_INVALID, "lsr_backward_levels: levels must be 1..LSR_MAX_LEVELS (4)");
+    if (a->reserved != 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: reserved must be 0");
+    if (a->P < 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: P must not be negative");
+    if (a->num_rendered < 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: num_rendered must not be negative");
+    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_backward_levels: needs settings.include_feature");
+    const int P = a->P, W = s->image_width, H = s->image_height, levels = a->levels;
+    if (W <= 0 || H <= 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: invalid settings.image_width / image_height");
+    if (P > 0) {
+        if (!a->geom_buffer) return fail(LSR_ERR_INVALID, "lsr_backward_levels: geom_buffer is NULL");
+        if (!a->binning_buffer) return fail(LSR_ERR_INVALID, "lsr_backward_levels: binning_buffer is NULL");
+        if (!a->image_buffer) return fail(LSR_ERR_INVALID, "lsr_backward_levels: image_buffer is NULL");
+        if (!a->radii) return fail(LSR_ERR_INVALID, "lsr_backward_levels: radii is NULL");
+        if (!a->scratch) return fail(LSR_ERR_INVALID, "lsr_backward_levels: scratch is NULL");
+        if (!a->dL_dlanguage_feature) return fail(LSR_ERR_INVALID, "lsr_backward_levels: dL_dlanguage_feature is NULL");
+        if ((a->raw & LSR_RAW_LANGUAGE) && !a->language_feature)
+            return fail(LSR_ERR_INVALID, "lsr_backward_levels: language_feature is NULL with raw & LSR_RAW_LANGUAGE");
+    }
+    const int fused = (a->out_language_feature ? 1 : 0) + (a->loss_target ? 1 : 0) + (a->loss_mask ? 1 : 0) +
+                      (a->dL_dloss ? 1 : 0);
+    if (fused != 0 && fused != 4)
+        return fail(LSR_ERR_INVALID, "lsr_backward_levels: the fused seed needs out_language_feature, loss_target, "
+                                     "loss_mask and dL_dloss, all four or none");
+    if (fused == 0 && !a->dL_dout_language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_backward_levels: no seed, give dL_dout_language_feature or the fused seed "
+                                     "(dL_dloss)");
+    if (P == 0) return LSR_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = s->debug != 0;
+    if (a->num_rendered == 0) {  // nothing was drawn: no Gaussian has a weight in any pixel
+        LSR_TRY(zero_fill(a->dL_dlanguage_feature, sizeof(float) * 3 * (size_t)levels * (size_t)P, stream),
+                "memset dlang levels");
+        return LSR_OK;
+    }
+    const Layout L = make_layout(P, W, H, a->num_rendered, 0);  // point_list sits at offset 0
+    char* geom = static_cast<char*>(a->geom_buffer);
+    char* image = static_cast<char*>(a->image_buffer);
+    char* binning = static_cast<char*>(a->binning_buffer);
+    float* acc = static_cast<float*>(a->scratch);
+    LSR_TRY(zero_fill(acc, sizeof(float) * 3 * (size_t)levels * (size_t)P, stream), "memset levels grad");
+    LevelsGradParams gp{};
+    gp.r.W = W;
+    gp.r.H = H;
+    gp.r.gx = L.gx;
+    gp.r.gy = L.gy;
+    gp.r.ranges = reinterpret_cast<const uint2*>(image + L.ranges);
+    gp.r.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
+    gp.r.record = reinterpret_cast<const float4*>(geom + L.record);
+    gp.r.sched_counts = reinterpret_cast<uint32_t*>(image + L.counters);
+    gp.r.sched_lists = reinterpret_cast<uint32_t*>(image + L.tile_lists);
+    gp.levels = levels;
+    gp.dL_dout = a->dL_dout_language_feature;
+    gp.out_lang = a->out_language_feature;
+    gp.loss_gt = a->loss_target;
+    gp.loss_mask = a->loss_mask;
+    gp.dL_dloss = a->dL_dloss;
+    gp.acc = acc;
+    LSR_TRY(launch_render_levels_grad(gp, L.tiles, stream), "render levels grad");
+    LSR_TRY(launch_levels_grad_epilogue(P, levels, a->radii, acc, (a->raw & LSR_RAW_LANGUAGE) ? a->language_feature : nullptr,
+                                        a->dL_dlanguage_feature, stream),
+            "levels grad epilogue");
+    return LSR_OK;
+}
+
 int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_alloc_fn alloc, void* user,
                      void* stream_ptr)
 {

@@ -544,6 +544,25 @@ int render_forward_occupancy(int levels);  // lsr_debug_levels_occupancy
 hipError_t launch_fill_levels(int P, int levels, const float* more, int raw, const int32_t* radii, float4* lev,
                               hipStream_t s);
 hipError_t launch_render_backward(const RenderParams& p, int tiles, hipStream_t s);
+// lsr_backward_levels: the language gradient of `levels` levels by the forward's walk run again.  r
+// holds what that walk reads of the inference forward's buffers (W, H, gx, gy, ranges, point_list,
+// record, sched_counts, sched_lists).  Seeds: dL_dout (levels x 3 x HW) and / or the fused masked-L1
+// seed (out_lang, loss_gt: levels x 3 x HW; loss_mask: levels x HW bytes; dL_dloss: levels floats, all
+// four or none).  acc: P rows of 3 levels floats, zeroed, to which the kernel adds.
+struct LevelsGradParams {
+    RenderParams r;
+    int levels;  // 1 .. LSR_MAX_LEVELS
+    const float* dL_dout;
+    const float *out_lang, *loss_gt;
+    const uint8_t* loss_mask;
+    const float* dL_dloss;
+    float* acc;
+};
+hipError_t launch_render_levels_grad(const LevelsGradParams& p, int tiles, hipStream_t s);
+// acc -> dL_dlanguage_feature (levels x P x 3): zeros where radii <= 0; lang (the raw features, levels x
+// P x 3) chains the normalisation, null: the gradient of the activated features
+hipError_t launch_levels_grad_epilogue(int P, int levels, const int32_t* radii, const float* acc, const float* lang,
+                                       float* out, hipStream_t s);
 // the fused loss of an empty scene (P == 0: no render forward runs) into p.out_loss
 hipError_t launch_loss_background(const RenderParams& p, hipStream_t s);
 hipError_t render_stats_read(unsigned long long* out, int n);  // reads and clears

@@ -1714,4 +1714,201 @@ hipError_t launch_render_backward(const RenderParams& pin, int tiles, hipStream_
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// multi-level language gradient (lsr_backward_levels): the backward of lsr_forward_levels
+// ------------------------------------------------------------------------------------------
+// With the geometry frozen the only gradient is the one of the activated level features, and
+//   dL/da[l][k][c] = sum over pixels of w_k g[l][c],   w_k = alpha_k T_k,   g = dL/d(level l's map),
+// where w_k is the forward's own blend weight: zero for an entry that fails the alpha tests and for
+// every entry after the pixel stopped.  T_k is the forward's running product, so the sum is taken
+// front to back by the forward's walk run again (stage, wave_compact, walk_list over walk_pair_alpha:
+// the same alphas, cuts and 1e-4 stop) -- no final T, contributor counts, cover bytes, split states
+// or work lists, none of which the inference forward writes.  Per pixel the kernel carries T and the
+// 3 kLevels seeds; per visited entry the partials w g are reduced over the wave (the backward's
+// reduce-scatter; entries no lane blends are skipped by a ballot), the four waves' totals meet in LDS
+// and after each batch every (tile, Gaussian) pair some lane blended adds one row of 3 kLevels floats
+// to the Gaussian's accumulator row (consecutive lanes, consecutive floats of a row).
+//
+// A pixel whose seeds are all zero (a masked pixel, one outside the image) adds nothing to any sum:
+// it starts as done, so a wave stops when its seeded pixels have.
+
+// One pixel's 3 kLevels seeds: dL_dout's values, plus the fused masked-L1 seed
+// dL_dloss[l] sign(f m - gt m) m / (3 HW) (bwd_pixel_init's expression, from the map itself).
+template <int kLevels>
+__device__ __forceinline__ void levels_seed(const LevelsGradParams& gp, bool inside, size_t pix, size_t HW,
+                                            float (&g)[3 * kLevels])
+{
+#pragma unroll
+    for (int k = 0; k < 3 * kLevels; k++) g[k] = 0.0f;
+    if (!inside) return;
+    if (gp.dL_dout) {
+#pragma unroll
+        for (int k = 0; k < 3 * kLevels; k++) g[k] = gp.dL_dout[(size_t)k * HW + pix];
+    }
+    if (gp.dL_dloss) {
+#pragma unroll
+        for (int l = 0; l < kLevels; l++) {
+            const float m = gp.loss_mask[(size_t)l * HW + pix] ? 1.0f : 0.0f;
+            const float gN = gp.dL_dloss[l] * (1.0f / (float)(3 * (int64_t)HW));
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const size_t at = (size_t)(3 * l + c) * HW + pix;
+                const float d = gp.out_lang[at] * m - gp.loss_gt[at] * m;
+                const float sg = d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f);
+                g[3 * l + c] += gN * sg * m;
+            }
+        }
+    }
+}
+
+template <int kLevels>
+__global__ __launch_bounds__(kTilePixels) void k_render_levels_grad(LevelsGradParams gp)
+{
+    static_assert(kLevels >= 1 && kLevels <= LSR_MAX_LEVELS && 3 * LSR_MAX_LEVELS == 12,
+                  "the reduce-scatter carries 12 values");
+    constexpr int kThreads = kTilePixels;
+    constexpr int kV = 3 * kLevels;  // values per (tile, Gaussian) row
+    const RenderParams& p = gp.r;
+    __shared__ float4 sA[kThreads];   // x, y, -0.5 conic.x, -0.5 conic.z
+    __shared__ float4 sB[kThreads];   // conic.y, opacity, power cutoff, -
+    __shared__ uint8_t sM[kThreads];  // entry_cover mask
+    // per-wave culled slot lists as in k_render_forward (byte offsets 16 s, four zero slots past the end)
+    __shared__ __attribute__((aligned(8))) uint16_t sL[kThreads / 64][kThreads + 8];
+    __shared__ float sG[kThreads * kV];   // the batch's per-entry sums of the tile
+    __shared__ uint32_t s_gid[kThreads];  // the batch's Gaussian ids, for the flush
+
+    int tile = (int)blockIdx.x;
+    if (p.sched_counts) {  // tiles without entries are not listed: nothing to add
+        tile = scheduled_tile((int)blockIdx.x, p.sched_counts + kCntFwdClass, p.sched_lists, p.gx * p.gy);
+        if (tile < 0) return;
+    }
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const auto [px, py, pxy, tx0, ty0, inside] = tile_pixel(p, tile, t);
+    const uint2 range = p.ranges[tile];
+    const uint32_t start = range.x, end = range.y;
+
+    float g[kV];
+    levels_seed<kLevels>(gp, inside, (size_t)py * p.W + px, (size_t)p.W * p.H, g);
+    bool seeded = false;
+#pragma unroll
+    for (int k = 0; k < kV; k++) seeded = seeded || g[k] != 0.0f;
+    float T = seeded ? 1.0f : -1.0f;  // walk_list's state: > 0 while the pixel composites
+
+    // this lane's value of the reduce-scatter and its slot in an entry's row (one level: the five-value
+    // form, whose values 9..11 carry the row)
+    // (scatter_index / scatter_writer and their five-value forms written out: called from here, they
+    // change the backward kernels' code, tools/isa_same.py)
+    const bool b2 = lane & 4, b3 = lane & 8, b4 = lane & 16, b5 = lane & 32;
+    const int vidx = kLevels == 1 ? (b3 ? 2 : (b4 ? (b5 ? 1 : -1) : (b5 ? 0 : -1)))
+                                  : (b2 ? 2 : (b3 ? 1 : 0)) + (b4 ? 3 : 0) + (b5 ? 6 : 0);
+    const bool one = kLevels == 1 ? (lane & 7) == 0 && (!b3 || (lane & 48) == 0) : (lane & 3) == 0 && !(b2 && b3);
+    const bool writer = one && vidx >= 0 && vidx < kV;
+    float* const sGl = sG + (writer ? vidx : 0);
+
+    uint32_t g_next = start + t < end ? p.point_list[start + t] : 0u;
+    for (uint32_t base = start; base < end; base += kThreads) {
+        // (also the barrier between the last batch's flush and this batch's stores)
+        if (__syncthreads_count(T < 0.0f) == kThreads) break;
+        const uint32_t idx = base + t;
+        if (idx < end) {
+            const uint32_t gi = g_next;
+            const float4 a = p.record[3 * (size_t)gi];
+            const float4 b = p.record[3 * (size_t)gi + 1];
+            // stage_entry's records and cover test (no colour or feature record: the gradient of the
+            // features does not read them)
+            const float cut = power_cutoff(b.y);
+            sA[t] = make_float4(a.x, a.y, -0.5f * a.z, -0.5f * b.x);
+            sB[t] = make_float4(a.w, b.y, cut, 0.0f);
+            sM[t] = (uint8_t)entry_cover(a.x, a.y, a.z, a.w, b.x, cut, tx0, ty0);
+            s_gid[t] = gi;
+        }
+        for (int i = t; i < kThreads * kV; i += kThreads) sG[i] = 0.0f;
+        __syncthreads();
+        const int cnt = (int)min((uint32_t)kThreads, end - base);
+        const int n = wave_compact(sM, cnt, 1u << wave, lane, sL[wave]);
+        __syncthreads();  // list visible to the wave's other lanes
+        if (idx + kThreads < end) g_next = p.point_list[idx + kThreads];
+        walk_list(sL[wave], n, sA, sB, pxy, T, [&](float al, bool ok, uint32_t o) {
+            // fwd_pixel_blend's weight and transmittance update
+            const float a = ok ? al : 0.0f;
+            const float test_T = T * (1.0f - a);
+            const bool go = !(test_T < 0.0001f);
+            const float w = go ? a * T : 0.0f;
+            T = go ? test_T : -fabsf(T);
+            if (__ballot(w != 0.0f) == 0ull) return;  // no lane blends the entry (wave-uniform)
+            float v[12];
+            float tot;
+            if (kLevels == 1) {
+                v[9] = w * g[0];
+                v[10] = w * g[1];
+                v[11] = w * g[2];
+                v[0] = v[1] = 0.0f;
+                tot = wave_reduce_scatter5(v, lane);
+            } else {
+#pragma unroll
+                for (int k = 0; k < kV; k++) v[k] = w * g[k];
+#pragma unroll
+                for (int k = kV; k < 12; k++) v[k] = 0.0f;
+                tot = wave_reduce_scatter12(v, lane);
+            }
+            // o = 16 x the entry's batch slot: its row starts at float kV (o / 16)
+            if (writer) atomicAdd(sGl + (o >> 4) * (uint32_t)kV, tot);
+        });
+        __syncthreads();
+        // flush: the batch's kV x cnt sums on consecutive threads -> one atomic row per (tile, Gaussian)
+        // that some lane blended (a sum that is exactly zero adds nothing)
+        for (int slot = t; slot < cnt * kV; slot += kThreads) {
+            const float v = sG[slot];
+            if (v == 0.0f) continue;
+            const int e = slot / kV, c = slot - kV * e;
+            atomicAdd(gp.acc + (size_t)s_gid[e] * kV + c, v);
+        }
+    }
+}
+
+// One thread per Gaussian: its accumulator row -> dL_dlanguage_feature (levels x P x 3), through the
+// normalisation's chain rule when `lang` (the raw features, levels x P x 3) is given; exact zeros for
+// culled Gaussians.  Every entry of the output is written.
+__global__ __launch_bounds__(256) void k_levels_grad_epilogue(int P, int levels, const int32_t* __restrict__ radii,
+                                                              const float* __restrict__ acc,
+                                                              const float* __restrict__ lang, float* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const bool live = radii[i] > 0;
+    const float* row = acc + (size_t)i * 3 * levels;
+    for (int l = 0; l < levels; l++) {
+        const size_t at = ((size_t)l * P + i) * 3;
+        float3 d = make_float3(0.f, 0.f, 0.f);
+        if (live) {
+            d = make_float3(row[3 * l], row[3 * l + 1], row[3 * l + 2]);
+            if (lang) d = act_lang_backward(lang[at], lang[at + 1], lang[at + 2], d.x, d.y, d.z);
+        }
+        out[at] = d.x;
+        out[at + 1] = d.y;
+        out[at + 2] = d.z;
+    }
+}
+
+hipError_t launch_render_levels_grad(const LevelsGradParams& gp, int tiles, hipStream_t s)
+{
+    if (tiles == 0) return hipSuccess;
+    const dim3 grid(tiles), block(kTilePixels);
+    if (gp.levels == 1) hipLaunchKernelGGL(k_render_levels_grad<1>, grid, block, 0, s, gp);
+    else if (gp.levels == 2) hipLaunchKernelGGL(k_render_levels_grad<2>, grid, block, 0, s, gp);
+    else if (gp.levels == 3) hipLaunchKernelGGL(k_render_levels_grad<3>, grid, block, 0, s, gp);
+    else if (gp.levels == 4) hipLaunchKernelGGL(k_render_levels_grad<4>, grid, block, 0, s, gp);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_levels_grad_epilogue(int P, int levels, const int32_t* radii, const float* acc, const float* lang,
+                                       float* out, hipStream_t s)
+{
+    if (P == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_levels_grad_epilogue, dim3((P + 255) / 256), dim3(256), 0, s, P, levels, radii, acc, lang,
+                       out);
+    return hipGetLastError();
+}
+
 }  // namespace lsr
