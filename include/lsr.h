@@ -760,6 +760,104 @@ typedef struct lsr_backward_levels_args {
 size_t lsr_backward_levels_bytes(int32_t P, int32_t levels);
 int32_t lsr_backward_levels(const lsr_settings* settings, const lsr_backward_levels_args* args, void* stream);
 
+/* ---- the joint levels step without a host wait (for a HIP graph capture) --------------------------
+ * lsr_levels_step_forward is lsr_forward_levels in capacity mode, optionally split in phases;
+ * lsr_levels_step_backward is lsr_backward_levels on that forward's buffers, optionally with the Adam
+ * step of the (levels, P, 3) raw features and the next forward's feature fills fused into its
+ * per-Gaussian tail (langsplat_amd.levels_graph.GraphedLevelsStep).  lsr_forward_levels and
+ * lsr_backward_levels keep their contracts; neither call here ever waits for the device.
+ *
+ * lsr_levels_step_forward.  fwd.capacity_rendered > 0, fwd.capacity_entries > 0 and fwd.overflow are
+ * required; *num_rendered returns fwd.capacity_rendered (as lsr_forward in capacity mode).  A view over
+ * a capacity sets *fwd.overflow to 0x3F800000 (else 0) and is not binned: every tile range stays empty
+ * and no tile is scheduled, so the call leaves zeros in every level's map and the background colour in
+ * out_color (radii and `visible` are still the preprocess's).  A view that draws nothing (true count 0)
+ * leaves the same images with *fwd.overflow == 0.  fwd.phase:
+ *     LSR_PHASE_ALL               geometry, the feature fills, the compositing;
+ *     LSR_PHASE_COMPOSITE         the geometry is already in the buffer set -- from a plain
+ *                                 lsr_forward(phase = LSR_PHASE_GEOMETRY) with the same settings, P,
+ *                                 capacities, flags and allocator (the geometry does not depend on the
+ *                                 levels), or from lsr_view_restore of a pack saved from such a call --
+ *                                 and this call writes the visible Gaussians' level-0 slots of the
+ *                                 records and their LSR_BUF_LEVELS rows from the features, then composites;
+ *     LSR_PHASE_COMPOSITE_FILLED  records and LSR_BUF_LEVELS hold the activated features already
+ *                                 (lsr_levels_step_backward's fill_record / fill_levels): compositing only.
+ * In the two composite phases fwd.radii is an input (what the geometry call or the restore left there)
+ * and fwd.visible is not written: both belong to the phase that runs the preprocess.
+ * LSR_PHASE_GEOMETRY is refused (use lsr_forward).  levels == 1 is lsr_forward's own capacity path.
+ * P == 0 is served as by lsr_forward_levels (zero images, nothing else; *fwd.overflow is not written).
+ * Refused with LSR_ERR_INVALID before any device work, the message naming the field: what
+ * lsr_forward_levels refuses (levels, reserved, include_feature, fwd.flags != LSR_FWD_NO_BACKWARD,
+ * loss_target / loss_mask / out_loss, language_ready, NULL features or outputs), fwd.capacity_rendered
+ * or fwd.capacity_entries <= 0, a NULL fwd.overflow, and fwd.phase == LSR_PHASE_GEOMETRY or unknown.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+typedef struct lsr_levels_step_forward_args {
+    lsr_forward_levels_args levels;        /* as lsr_forward_levels, with the differences above */
+    int32_t reserved;                      /* 0 */
+} lsr_levels_step_forward_args;
+int32_t lsr_levels_step_forward(const lsr_settings* settings, const lsr_levels_step_forward_args* args,
+                                lsr_alloc_fn alloc, void* alloc_user, void* stream, int64_t* num_rendered);
+
+/* lsr_levels_step_backward.  The fields shared with lsr_backward_levels_args mean what they mean there;
+ * the buffers are those of a lsr_levels_step_forward call (any phase) and num_rendered is the value it
+ * returned, i.e. its capacity (> 0 when P > 0).  The call cannot know whether anything was drawn: a
+ * view whose true count is 0 and a view over capacity both leave empty tile ranges and no scheduled
+ * tile, the gradient walk then adds nothing and the gradient is exact zeros.  The walk is
+ * lsr_backward_levels' kernel.  The tail, one pass per Gaussian and level:
+ *     update == NULL   dL_dlanguage_feature as lsr_backward_levels writes it (it is then required;
+ *                      update_step_dev, update_skip, fill_record and fill_levels must be NULL);
+ *     update != NULL   needs raw & LSR_RAW_LANGUAGE, update->param == language_feature, update->n ==
+ *                      3 levels P, the moments and update_step_dev (lsr_adam_multi's device block: word 0
+ *                      the count, LSR_ADAM_WORD_LR the learning rate; update->step is the offset;
+ *                      update->grad and update->lr are not read).  A one-wave launch advances the step
+ *                      block; then per value: the raw gradient (exact zeros where radii <= 0), written
+ *                      to dL_dlanguage_feature when that is not NULL, and the Adam step of the feature
+ *                      and its moments -- the operations of the update == NULL tail followed by
+ *                      lsr_adam_multi(step_dev), bit for bit.  *update_skip != 0 (update_skip may be
+ *                      NULL: never): no feature, moment or count changes, the skipped count grows by 1.
+ *                      fill_record (another call's, or this set's, render records,
+ *                      lsr_state_layout.record) receives level 0's activated updated feature in the
+ *                      language slots of EVERY Gaussian, and fill_levels (a LSR_BUF_LEVELS array,
+ *                      lsr_levels_bytes(P, levels)) the other levels' in lsr_forward_levels' layout,
+ *                      zero padded -- skipped or not, visible or not (lsr_backward_args.fill_record's
+ *                      rule) -- so the next lsr_levels_step_forward runs LSR_PHASE_COMPOSITE_FILLED.
+ * P == 0: a no-op that returns LSR_OK after the argument checks (nothing is enqueued, the step block
+ * does not advance).
+ * Refused with LSR_ERR_INVALID before any device work, the message naming the field: what
+ * lsr_backward_levels refuses (dL_dlanguage_feature may be NULL with update); num_rendered == 0 with
+ * P > 0; update without raw & LSR_RAW_LANGUAGE; update->param != language_feature; update->n != 3 levels
+ * P; NULL update->exp_avg / exp_avg_sq or update_step_dev; fill_levels NULL with levels > 1 and
+ * fill_record set, or fill_levels set without fill_record; update_step_dev, update_skip, fill_record or
+ * fill_levels without update.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+typedef struct lsr_levels_step_backward_args {
+    int32_t P;
+    int32_t levels;                         /* 1 .. LSR_MAX_LEVELS */
+    int32_t raw;                            /* lsr_raw_flags; only LSR_RAW_LANGUAGE is read */
+    int32_t reserved;                       /* 0 */
+    int64_t num_rendered;                   /* value returned by lsr_levels_step_forward (its capacity) */
+    void* geom_buffer;                      /* the forward's three buffers */
+    void* binning_buffer;
+    void* image_buffer;
+    const int32_t* radii;                   /* P, the forward's */
+    const float* language_feature;          /* levels x P x 3, level-major; read iff raw & LSR_RAW_LANGUAGE */
+    const float* dL_dout_language_feature;  /* levels x 3 x H x W, or NULL */
+    const float* out_language_feature;      /* fused seed: the forward's maps, levels x 3 x H x W, or NULL */
+    const float* loss_target;               /* fused seed: levels x 3 x H x W, or NULL */
+    const uint8_t* loss_mask;               /* fused seed: levels x H x W bool bytes, or NULL */
+    const float* dL_dloss;                  /* fused seed: levels device floats, or NULL */
+    void* scratch;                          /* lsr_backward_levels_bytes(P, levels) bytes */
+    float* dL_dlanguage_feature;            /* levels x P x 3; may be NULL with update */
+    const lsr_adam_tensor* update;          /* the fused Adam step of language_feature, or NULL */
+    int64_t* update_step_dev;               /* device int64[LSR_ADAM_STEP_WORDS] */
+    const int32_t* update_skip;             /* device int32 (the forward's overflow flag), or NULL */
+    float* fill_record;                     /* render records receiving level 0, or NULL */
+    void* fill_levels;                      /* LSR_BUF_LEVELS array receiving levels 1.., or NULL */
+    int64_t reserved2;                      /* 0 */
+} lsr_levels_step_backward_args;
+int32_t lsr_levels_step_backward(const lsr_settings* settings, const lsr_levels_step_backward_args* args,
+                                 void* stream);
+
 /* ---- a view's frozen geometry, kept across steps of the language stage ---------------------------
  * In the language stage every geometry parameter is frozen (scene/gaussian_model.py:203-217), and
  * train.py:85-87 draws each of a scene's views again every epoch: for one camera, what a

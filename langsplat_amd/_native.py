@@ -81,6 +81,16 @@ class LsrAdamTensor(ctypes.Structure):
                 ("eps", ctypes.c_double), ("step", ctypes.c_int64)]
 
 
+class LsrLevelsStepForwardArgs(ctypes.Structure):
+    _fields_ = [("levels", LsrForwardLevelsArgs), ("reserved", ctypes.c_int32)]
+
+
+class LsrLevelsStepBackwardArgs(ctypes.Structure):
+    _fields_ = LsrBackwardLevelsArgs._fields_ + [
+        ("update", ctypes.POINTER(LsrAdamTensor)), ("update_step_dev", _vp), ("update_skip", _vp),
+        ("fill_record", _vp), ("fill_levels", _vp), ("reserved2", ctypes.c_int64)]
+
+
 class LsrBackwardArgs(ctypes.Structure):
     _fields_ = [("P", ctypes.c_int32), ("M", ctypes.c_int32), ("num_rendered", ctypes.c_int64)] + [
         (n, _vp) for n in ("means3D", "shs", "colors_precomp", "language_feature", "opacities", "scales",
@@ -171,6 +181,10 @@ SIGNATURES = {
                                             ALLOC_FN, _vp, _vp, ctypes.POINTER(ctypes.c_int64)]),
     "lsr_backward_levels_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
     "lsr_backward_levels": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrBackwardLevelsArgs), _vp]),
+    "lsr_levels_step_forward": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrLevelsStepForwardArgs),
+                                                 ALLOC_FN, _vp, _vp, ctypes.POINTER(ctypes.c_int64)]),
+    "lsr_levels_step_backward": (ctypes.c_int32, [ctypes.POINTER(LsrSettings),
+                                                  ctypes.POINTER(LsrLevelsStepBackwardArgs), _vp]),
     "lsr_mark_visible": (ctypes.c_int32, [ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "lsr_query_relevancy": (ctypes.c_int32, [ctypes.POINTER(LsrQueryArgs), _vp]),
     "lsr_eval_filter": (ctypes.c_int32, [ctypes.POINTER(LsrEvalFilterArgs), _vp]),
@@ -750,11 +764,14 @@ def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_featur
     if L > 1:
         la.more_language_feature = _ptr(lf[1:])
         la.more_out_language_feature = _ptr(langs[1:])
+    entries = ctypes.c_int64(0)
+    la.fwd.out_num_entries = ctypes.pointer(entries)
     alloc = _Allocator(device)
     nr = ctypes.c_int64(0)
     with _on_device(device), alloc:
         _check(lib.lsr_forward_levels(ctypes.byref(s), ctypes.byref(la), _ALLOC_CB, None, _stream(device),
                                       ctypes.byref(nr)), "lsr_forward_levels")
+    LAST_COUNTS[(P, W, H)] = (int(nr.value), int(entries.value))  # the capacities a later capture needs
     out = (int(nr.value), color, langs, radii)
     if with_visibility:
         out += (visible,)
@@ -808,6 +825,149 @@ def rasterize_gaussians_levels_backward(rs, language_features, radii, num_render
     a.dL_dlanguage_feature = _ptr(out)
     with _on_device(device):
         _check(lib.lsr_backward_levels(ctypes.byref(s), ctypes.byref(a), _stream(device)), "lsr_backward_levels")
+    return out
+
+
+def levels_step_forward(rs, means3D, shs, colors_precomp, language_features, opacities, scales, rotations,
+                        cov3D_precomp, raw=0, shs_rest=None):
+    """rasterize_gaussians_levels without a host wait (include/lsr.h lsr_levels_step_forward): needs an
+    active `capacity`, honours forward_phase (all, COMPOSITE, COMPOSITE_FILLED) and puts outputs and
+    scratch into the active static_buffers, as rasterize_gaussians does -- so a rasterize_gaussians
+    call in forward_phase.GEOMETRY (flags=FWD_NO_BACKWARD, language_features[0] as its feature) over the
+    same static_buffers supplies a composite phase's geometry (radii and `visible` are written by the
+    phase that runs the preprocess: give that call visible=output_tensor("visible", (P,), torch.bool,
+    device), the tensor returned here).  Returns (capacity, color (3, H, W),
+    language_images (L, 3, H, W), radii, visible (P,) bool, geom, binning, image, levels): the three
+    state buffers and the LSR_BUF_LEVELS array (empty for L == 1), for levels_step_backward."""
+    lib = load()
+    device = means3D.device
+    P = int(means3D.shape[0])
+    L = check_level_features(language_features, P)
+    cap = capacity.active()
+    if cap is None:
+        raise RuntimeError("levels_step_forward: capacity mode only (inside a _native.capacity block)")
+    H, W = int(rs.image_height), int(rs.image_width)
+    keep: list = []
+    s = make_settings(rs, keep)
+    lf = _f32c(language_features.detach())
+    color = output_tensor("color", (3, H, W), torch.float32, device)
+    langs = output_tensor("levels_language", (L, 3, H, W), torch.float32, device)
+    radii = output_tensor("radii", (P,), torch.int32, device)
+    visible = output_tensor("visible", (P,), torch.bool, device)
+    sa = LsrLevelsStepForwardArgs()
+    la = sa.levels
+    _fill_forward_args(la.fwd, means3D, shs, colors_precomp, lf, opacities, scales, rotations, cov3D_precomp, raw,
+                       FWD_NO_BACKWARD, shs_rest, color, langs, radii, visible)
+    la.levels = L
+    if L > 1:
+        la.more_language_feature = _ptr(lf[1:])
+        la.more_out_language_feature = _ptr(langs[1:])
+    la.fwd.phase = forward_phase.active()
+    la.fwd.capacity_rendered = cap.rendered
+    la.fwd.capacity_entries = cap.entries
+    la.fwd.overflow = _ptr(cap.overflow)
+    alloc = _Allocator(device)
+    nr = ctypes.c_int64(0)
+    with _on_device(device), alloc:
+        _check(lib.lsr_levels_step_forward(ctypes.byref(s), ctypes.byref(sa), _ALLOC_CB, None, _stream(device),
+                                           ctypes.byref(nr)), "lsr_levels_step_forward")
+    return (int(nr.value), color, langs, radii, visible, alloc.get(LSR_BUF_GEOM), alloc.get(LSR_BUF_BINNING),
+            alloc.get(LSR_BUF_IMAGE), alloc.get(LSR_BUF_LEVELS))
+
+
+class LevelsUpdate:
+    """levels_step_backward's fused Adam step (include/lsr.h lsr_levels_step_backward_args.update): the
+    raw (L, P, 3) features `param` with their moments, the hyper-parameters, the device step block
+    (int64[ADAM_STEP_WORDS]: the count, and at ADAM_WORD_LR the learning rate's bits) and this tensor's
+    offset from its count, the optional skip flag (device int32) and the optional fill targets: a
+    device address of render records (state_layout's "record" in a geometry buffer) and the
+    LSR_BUF_LEVELS array of that forward (a uint8 tensor; needed with L > 1)."""
+
+    def __init__(self, param, exp_avg, exp_avg_sq, betas, eps, step_dev, step_offset=0, skip=None, fill_record=None,
+                 fill_levels=None):
+        for t in (param, exp_avg, exp_avg_sq):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.shape != param.shape or t.device != param.device:
+                raise ValueError("LevelsUpdate: param, exp_avg and exp_avg_sq must be contiguous fp32 tensors of one "
+                                 "shape on one device")
+        if step_dev.dtype != torch.int64 or step_dev.numel() < ADAM_STEP_WORDS or step_dev.device != param.device:
+            raise ValueError(f"LevelsUpdate: step_dev must be int64[{ADAM_STEP_WORDS}] on the features' device")
+        if skip is not None and (skip.dtype != torch.int32 or skip.numel() != 1 or skip.device != param.device):
+            raise ValueError("LevelsUpdate: skip must be a one-element int32 tensor on the features' device")
+        self.param, self.exp_avg, self.exp_avg_sq = param, exp_avg, exp_avg_sq
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.step_dev, self.step_offset, self.skip = step_dev, int(step_offset), skip
+        self.fill_record, self.fill_levels = fill_record, fill_levels
+
+    def table(self) -> LsrAdamTensor:
+        return LsrAdamTensor(self.param.numel(), self.param.data_ptr(), None, self.exp_avg.data_ptr(),
+                             self.exp_avg_sq.data_ptr(), 0.0, self.betas[0], self.betas[1], self.eps, self.step_offset)
+
+
+def levels_step_backward(rs, language_features, radii, num_rendered, geom, binning, image, raw=0, grad_images=None,
+                         images=None, targets=None, masks=None, grad_losses=None, update: Optional[LevelsUpdate] = None,
+                         out=None, scratch=None, want_grad=True):
+    """rasterize_gaussians_levels_backward on a levels_step_forward's buffers, without a host wait
+    (include/lsr.h lsr_levels_step_backward); num_rendered is what that forward returned (its capacity).
+    update: the Adam step of language_features (and the next forward's feature fills) in the tail;
+    language_features must then be update.param itself.  out / scratch: persistent tensors for the
+    (L, P, 3) gradient and the accumulator (a captured step), else fresh ones; want_grad=False with
+    update writes no gradient tensor (returns None)."""
+    lib = load()
+    device = radii.device
+    P = int(radii.shape[0])
+    L = check_level_features(language_features, P)
+    H, W = int(rs.image_height), int(rs.image_width)
+    keep: list = []
+    s = make_settings(rs, keep)
+    fused = [images, targets, masks, grad_losses]
+    if any(x is not None for x in fused) and any(x is None for x in fused):
+        raise ValueError("levels_step_backward: images, targets, masks and grad_losses go together")
+    if grad_images is None and images is None:
+        raise ValueError("levels_step_backward: no seed (grad_images or the fused seed)")
+    a = LsrLevelsStepBackwardArgs()
+    a.P, a.levels, a.raw, a.num_rendered = P, L, int(raw) & RAW_LANGUAGE, int(num_rendered)
+    if update is not None:
+        if language_features is not update.param and language_features.data_ptr() != update.param.data_ptr():
+            raise ValueError("levels_step_backward: with update, language_features is update.param")
+        lf = update.param
+    else:
+        lf = _f32c(language_features.detach())
+    a.language_feature = _ptr(lf)
+    for name, t in (("grad_images", grad_images), ("images", images), ("targets", targets)):
+        if t is not None and tuple(t.shape) != (L, 3, H, W):
+            raise ValueError(f"levels_step_backward: {name} must be ({L}, 3, {H}, {W}), got {tuple(t.shape)}")
+    if grad_images is not None:
+        keep.append(_f32c(grad_images.detach()))
+        a.dL_dout_language_feature = keep[-1].data_ptr()
+    if images is not None:
+        if masks.dtype != torch.bool or tuple(masks.shape) != (L, H, W) or tuple(grad_losses.shape) != (L,):
+            raise ValueError(f"levels_step_backward: masks must be ({L}, {H}, {W}) bool and grad_losses ({L},)")
+        keep += [_f32c(images.detach()), _f32c(targets.detach()), masks.contiguous(), _f32c(grad_losses.detach())]
+        a.out_language_feature, a.loss_target, a.loss_mask, a.dL_dloss = (t.data_ptr() for t in keep[-4:])
+    if out is None and (want_grad or update is None):
+        out = torch.empty((L, P, 3), dtype=torch.float32, device=device)
+    nbytes = int(lib.lsr_backward_levels_bytes(P, L))
+    if scratch is None:
+        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    elif scratch.dtype != torch.uint8 or scratch.numel() < nbytes:
+        raise ValueError(f"levels_step_backward: scratch must be a uint8 tensor of at least {nbytes} bytes")
+    if out is not None and (tuple(out.shape) != (L, P, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
+        raise ValueError(f"levels_step_backward: out must be a contiguous fp32 ({L}, {P}, 3) tensor")
+    a.geom_buffer, a.binning_buffer, a.image_buffer = _ptr(geom), _ptr(binning), _ptr(image)
+    a.radii = _ptr(radii)
+    a.scratch = _ptr(scratch)
+    a.dL_dlanguage_feature = _ptr(out)
+    if update is not None:
+        tab = update.table()
+        keep.append(tab)
+        a.update = ctypes.pointer(tab)
+        a.update_step_dev = _vp(update.step_dev.data_ptr())
+        a.update_skip = _ptr(update.skip)
+        a.fill_record = None if update.fill_record is None else _vp(int(update.fill_record))
+        a.fill_levels = _ptr(update.fill_levels)
+    with _on_device(device):
+        _check(lib.lsr_levels_step_backward(ctypes.byref(s), ctypes.byref(a), _stream(device)),
+               "lsr_levels_step_backward")
     return out
 
 

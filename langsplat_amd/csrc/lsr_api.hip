@@ -265,6 +265,40 @@ struct LevelsCall {
     float4* lev;
 };
 
+// The gradient walk of lsr_backward_levels and lsr_levels_step_backward (A: either args struct, validated
+// by its entry point; P > 0, num_rendered > 0): clears the accumulator (a->scratch) and adds every
+// level's per-Gaussian sums to it.
+template <class A>
+static int32_t levels_grad_walk(const lsr_settings* s, const A* a, hipStream_t stream, bool debug)
+{
+    const int P = a->P, W = s->image_width, H = s->image_height, levels = a->levels;
+    const Layout L = make_layout(P, W, H, a->num_rendered, 0);  // point_list sits at offset 0
+    char* geom = static_cast<char*>(a->geom_buffer);
+    char* image = static_cast<char*>(a->image_buffer);
+    char* binning = static_cast<char*>(a->binning_buffer);
+    float* acc = static_cast<float*>(a->scratch);
+    LSR_TRY(zero_fill(acc, sizeof(float) * 3 * (size_t)levels * (size_t)P, stream), "memset levels grad");
+    LevelsGradParams gp{};
+    gp.r.W = W;
+    gp.r.H = H;
+    gp.r.gx = L.gx;
+    gp.r.gy = L.gy;
+    gp.r.ranges = reinterpret_cast<const uint2*>(image + L.ranges);
+    gp.r.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
+    gp.r.record = reinterpret_cast<const float4*>(geom + L.record);
+    gp.r.sched_counts = reinterpret_cast<uint32_t*>(image + L.counters);
+    gp.r.sched_lists = reinterpret_cast<uint32_t*>(image + L.tile_lists);
+    gp.levels = levels;
+    gp.dL_dout = a->dL_dout_language_feature;
+    gp.out_lang = a->out_language_feature;
+    gp.loss_gt = a->loss_target;
+    gp.loss_mask = a->loss_mask;
+    gp.dL_dloss = a->dL_dloss;
+    gp.acc = acc;
+    LSR_TRY(launch_render_levels_grad(gp, L.tiles, stream), "render levels grad");
+    return LSR_OK;
+}
+
 // The render forward of lsr_forward (both modes), after the binning.  lv: lsr_forward_levels' form.
 static int32_t render_forward_and_finish(const lsr_settings* s, const lsr_forward_args* a, const Layout& L, char* geom,
                                          char* image, char* binning, HostBlock* hb, hipStream_t stream, bool debug,
@@ -325,7 +359,8 @@ static int32_t render_forward_and_finish(const lsr_settings* s, const lsr_forwar
 }
 
 // lsr_forward, and with lv lsr_forward_levels (validated there: inference, one phase, no capacity
-// mode, no fused loss, no deferred feature).
+// mode, no fused loss, no deferred feature) or lsr_levels_step_forward (capacity mode; all phases but
+// the geometry one).
 static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
                             void* stream_ptr, int64_t* num_rendered, LevelsCall* lv);
 
@@ -525,11 +560,13 @@ static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, ls
         char* binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, L.binning_bytes));
         if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
         *num_rendered = R_cap;
-        if (deferred && a->phase == LSR_PHASE_COMPOSITE)
+        if (deferred && a->phase == LSR_PHASE_COMPOSITE) {
             LSR_TRY(launch_fill_language(P, a->language_feature, a->raw, a->radii,
                                          reinterpret_cast<float4*>(geom + L.record), stream),
                     "fill language");
-        return render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug);
+            if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
+        }
+        return render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
     }
     LSR_TRY(launch_preprocess(pp, stream), "preprocess");
     hm.mark();
@@ -569,7 +606,9 @@ static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, ls
         *num_rendered = R_cap;
         if (a->phase == LSR_PHASE_GEOMETRY) return LSR_OK;
         if (deferred) LSR_TRY(wait_and_fill_language(a, L, geom, stream), "fill language");
-        return render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug);
+        // (lsr_levels_step_forward, one phase: level 0 went into the records in the preprocess)
+        if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
+        return render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
     }
     const uint32_t seq = ++hb->seq == 0 ? ++hb->seq : hb->seq;
     LSR_TRY(launch_publish_counters((P + kPreThreads - 1) / kPreThreads, pp.partial, counters, hb->slot, seq,
@@ -730,33 +769,131 @@ int32_t lsr_backward_levels(const lsr_settings* s, const lsr_backward_levels_arg
                 "memset dlang levels");
         return LSR_OK;
     }
-    const Layout L = make_layout(P, W, H, a->num_rendered, 0);  // point_list sits at offset 0
-    char* geom = static_cast<char*>(a->geom_buffer);
-    char* image = static_cast<char*>(a->image_buffer);
-    char* binning = static_cast<char*>(a->binning_buffer);
-    float* acc = static_cast<float*>(a->scratch);
-    LSR_TRY(zero_fill(acc, sizeof(float) * 3 * (size_t)levels * (size_t)P, stream), "memset levels grad");
-    LevelsGradParams gp{};
-    gp.r.W = W;
-    gp.r.H = H;
-    gp.r.gx = L.gx;
-    gp.r.gy = L.gy;
-    gp.r.ranges = reinterpret_cast<const uint2*>(image + L.ranges);
-    gp.r.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
-    gp.r.record = reinterpret_cast<const float4*>(geom + L.record);
-    gp.r.sched_counts = reinterpret_cast<uint32_t*>(image + L.counters);
-    gp.r.sched_lists = reinterpret_cast<uint32_t*>(image + L.tile_lists);
-    gp.levels = levels;
-    gp.dL_dout = a->dL_dout_language_feature;
-    gp.out_lang = a->out_language_feature;
-    gp.loss_gt = a->loss_target;
-    gp.loss_mask = a->loss_mask;
-    gp.dL_dloss = a->dL_dloss;
-    gp.acc = acc;
-    LSR_TRY(launch_render_levels_grad(gp, L.tiles, stream), "render levels grad");
-    LSR_TRY(launch_levels_grad_epilogue(P, levels, a->radii, acc, (a->raw & LSR_RAW_LANGUAGE) ? a->language_feature : nullptr,
+    if (const int32_t rc = levels_grad_walk(s, a, stream, debug)) return rc;
+    LSR_TRY(launch_levels_grad_epilogue(P, levels, a->radii, static_cast<float*>(a->scratch),
+                                        (a->raw & LSR_RAW_LANGUAGE) ? a->language_feature : nullptr,
                                         a->dL_dlanguage_feature, stream),
             "levels grad epilogue");
+    return LSR_OK;
+}
+
+int32_t lsr_levels_step_forward(const lsr_settings* s, const lsr_levels_step_forward_args* sa, lsr_alloc_fn alloc,
+                                void* user, void* stream_ptr, int64_t* num_rendered)
+{
+    if (!s || !sa || !alloc || !num_rendered) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: null argument");
+    const lsr_forward_levels_args* la = &sa->levels;
+    const lsr_forward_args* a = &la->fwd;
+    if (la->levels < 1 || la->levels > LSR_MAX_LEVELS)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: levels must be 1..LSR_MAX_LEVELS (4)");
+    if (sa->reserved != 0 || la->reserved != 0)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: reserved must be 0");
+    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: needs settings.include_feature");
+    if (a->flags != LSR_FWD_NO_BACKWARD)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.flags must be LSR_FWD_NO_BACKWARD (the gradient walk "
+                                     "needs no backward state)");
+    if (a->loss_target)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: no fused loss, fwd.loss_target must be NULL");
+    if (a->loss_mask) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: no fused loss, fwd.loss_mask must be NULL");
+    if (a->out_loss) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: no fused loss, fwd.out_loss must be NULL");
+    if (a->language_ready) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.language_ready must be NULL");
+    if (a->capacity_rendered <= 0)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: capacity mode only, fwd.capacity_rendered must be > 0");
+    if (a->capacity_entries <= 0)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: capacity mode only, fwd.capacity_entries must be > 0");
+    if (!a->overflow) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: capacity mode only, fwd.overflow is NULL");
+    if (a->phase == LSR_PHASE_GEOMETRY)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.phase LSR_PHASE_GEOMETRY is lsr_forward's (the "
+                                     "geometry does not depend on the levels): call lsr_forward with that phase");
+    if (a->phase != LSR_PHASE_ALL && a->phase != LSR_PHASE_COMPOSITE && a->phase != LSR_PHASE_COMPOSITE_FILLED)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.phase must be LSR_PHASE_ALL, LSR_PHASE_COMPOSITE or "
+                                     "LSR_PHASE_COMPOSITE_FILLED");
+    if (a->P > 0 && !a->language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.language_feature (level 0) is NULL");
+    if (la->levels > 1 && a->P > 0 && !la->more_language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: more_language_feature is NULL with levels > 1");
+    if (la->levels > 1 && !la->more_out_language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: more_out_language_feature is NULL with levels > 1");
+    if (la->levels == 1) return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, nullptr);
+    LevelsCall lv{la->levels, la->more_language_feature, la->more_out_language_feature, nullptr};
+    return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, &lv);
+}
+
+int32_t lsr_levels_step_backward(const lsr_settings* s, const lsr_levels_step_backward_args* a, void* stream_ptr)
+{
+    if (!s) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: settings is NULL");
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: args is NULL");
+    if (a->levels < 1 || a->levels > LSR_MAX_LEVELS)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: levels must be 1..LSR_MAX_LEVELS (4)");
+    if (a->reserved != 0 || a->reserved2 != 0)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: reserved must be 0");
+    if (a->P < 0) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: P must not be negative");
+    if (a->num_rendered < 0)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: num_rendered must not be negative");
+    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: needs settings.include_feature");
+    const int P = a->P, W = s->image_width, H = s->image_height, levels = a->levels;
+    if (W <= 0 || H <= 0)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: invalid settings.image_width / image_height");
+    if (P > 0) {
+        if (a->num_rendered == 0)
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: num_rendered is the forward's capacity, > 0");
+        if (!a->geom_buffer) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: geom_buffer is NULL");
+        if (!a->binning_buffer) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: binning_buffer is NULL");
+        if (!a->image_buffer) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: image_buffer is NULL");
+        if (!a->radii) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: radii is NULL");
+        if (!a->scratch) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: scratch is NULL");
+        if (!a->dL_dlanguage_feature && !a->update)
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: dL_dlanguage_feature is NULL without update");
+        if ((a->raw & LSR_RAW_LANGUAGE) && !a->language_feature)
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: language_feature is NULL with raw & LSR_RAW_LANGUAGE");
+    }
+    const int fused = (a->out_language_feature ? 1 : 0) + (a->loss_target ? 1 : 0) + (a->loss_mask ? 1 : 0) +
+                      (a->dL_dloss ? 1 : 0);
+    if (fused != 0 && fused != 4)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: the fused seed needs out_language_feature, loss_target, "
+                                     "loss_mask and dL_dloss, all four or none");
+    if (fused == 0 && !a->dL_dout_language_feature)
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: no seed, give dL_dout_language_feature or the fused "
+                                     "seed (dL_dloss)");
+    if (a->update) {
+        const lsr_adam_tensor& u = *a->update;
+        if (!(a->raw & LSR_RAW_LANGUAGE))
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: update needs raw & LSR_RAW_LANGUAGE (the raw "
+                                         "features are what Adam steps)");
+        if (u.param != a->language_feature)
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: update->param must be language_feature");
+        if (u.n != 3 * (int64_t)levels * (int64_t)P)
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: update->n must be 3 * levels * P");
+        if (P > 0 && (!u.exp_avg || !u.exp_avg_sq))
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: update->exp_avg / exp_avg_sq is NULL");
+        if (!a->update_step_dev) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: update_step_dev is NULL");
+        if (a->fill_record && levels > 1 && !a->fill_levels)
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: fill_levels is NULL with levels > 1 and fill_record");
+        if (a->fill_levels && !a->fill_record)
+            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: fill_levels needs fill_record");
+    } else if (a->update_step_dev || a->update_skip || a->fill_record || a->fill_levels) {
+        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: update_step_dev / update_skip / fill_record / "
+                                     "fill_levels need update");
+    }
+    if (P == 0) return LSR_OK;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = s->debug != 0;
+    // no early return for an empty view: num_rendered is the capacity.  A view that drew nothing, or
+    // one over capacity, left empty ranges and no scheduled tile: the walk's workgroups all return
+    if (const int32_t rc = levels_grad_walk(s, a, stream, debug)) return rc;
+    float* acc = static_cast<float*>(a->scratch);
+    if (!a->update) {
+        LSR_TRY(launch_levels_grad_epilogue(P, levels, a->radii, acc,
+                                            (a->raw & LSR_RAW_LANGUAGE) ? a->language_feature : nullptr,
+                                            a->dL_dlanguage_feature, stream),
+                "levels grad epilogue");
+        return LSR_OK;
+    }
+    const lsr_adam_tensor& u = *a->update;
+    AdamHyper h{u.lr, u.beta1, u.beta2, u.eps, u.step};
+    LSR_TRY(launch_levels_tail(P, levels, a->radii, acc, u.param, u.exp_avg, u.exp_avg_sq, a->dL_dlanguage_feature, h,
+                               a->update_step_dev, a->update_skip, reinterpret_cast<float4*>(a->fill_record),
+                               static_cast<float4*>(a->fill_levels), stream),
+            "levels tail");
     return LSR_OK;
 }
 

@@ -420,6 +420,14 @@ hipError_t launch_adam_multi(AdamTable& tab, float grad_scale, hipStream_t s);
 hipError_t launch_language_tail(int P, const int32_t* radii, const float* grad, float* lang, float* exp_avg,
                                 float* exp_avg_sq, float* dmeans2D, float* dlang, const AdamHyper& h, int64_t* step_dev,
                                 const int32_t* skip, float4* fill, int deferred, hipStream_t s);
+// lsr_levels_step_backward with update: k_adam_advance (one tensor, the skip flag), then one pass per
+// (Gaussian, level): k_levels_grad_epilogue's gradient from acc (P rows of 3 levels floats) and the raw
+// features lang (levels x P x 3) into dlang (may be null), the Adam step of lang and its moments
+// (nothing on *skip), and with fill_record the activated updated features of every Gaussian: level 0
+// into fill_record's language slots, levels 1.. into fill_levels (launch_fill_levels' layout)
+hipError_t launch_levels_tail(int P, int levels, const int32_t* radii, const float* acc, float* lang, float* exp_avg,
+                              float* exp_avg_sq, float* dlang, const AdamHyper& h, int64_t* step_dev, const int32_t* skip,
+                              float4* fill_record, float4* fill_levels, hipStream_t s);
 hipError_t launch_adam_fill(int P, const float* grad, float grad_scale, float* lang, float* exp_avg, float* exp_avg_sq,
                             const AdamHyper& h, int64_t* step_dev, const int32_t* skip, float4* fill, int raw,
                             hipStream_t s);

@@ -232,6 +232,107 @@ hipError_t launch_language_tail(int P, const int32_t* radii, const float* grad, 
     return hipGetLastError();
 }
 
+// The joint levels step's tail in one pass (lsr_levels_step_backward with update): what
+// k_levels_grad_epilogue writes (dlang of every level from the accumulator rows and the raw features),
+// then the Adam step of the raw (levels, P, 3) features from it (adam_one, the scalars k_adam_advance
+// formed: the operations of lsr_adam_multi after the epilogue, bit for bit), then -- fill set -- the
+// activated updated features into the next forward's feature slots: level 0 into the language slots
+// of the records (k_language_tail's stores), levels 1.. into the level array in k_fill_levels' layout
+// (level_quads float4 per Gaussian, level-major, zero padded), for every Gaussian.
+// One thread per (Gaussian, level), the level the fast index: thread t = kLevels i + l owns floats
+// 3 t .. 3 t + 2 of the accumulator (P rows of 3 kLevels), so a wave reads 768 contiguous bytes of
+// it as three dwords per lane; the feature and moment rows of level l sit at (l P + i) 3, so the
+// wave's lanes of one level read 12-byte rows of consecutive Gaussians (kLevels runs of <= 64 /
+// kLevels rows, each contiguous).  Per thread every load is issued before any use.  No LDS.
+template <int kLevels>
+__global__ __launch_bounds__(256) void k_levels_tail(int P, const int32_t* __restrict__ radii,
+                                                     const float* __restrict__ acc, float* __restrict__ lang,
+                                                     float* __restrict__ m, float* __restrict__ v,
+                                                     float* __restrict__ dlang,
+                                                     const int64_t* __restrict__ step_dev,
+                                                     const int32_t* __restrict__ skip, float4* __restrict__ fill_record,
+                                                     float4* __restrict__ fill_levels)
+{
+    constexpr int kE = 3 * (kLevels - 1), kQ = level_quads(kLevels);
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)P * kLevels) return;
+    const int i = (int)(t / kLevels), lvl = (int)(t - (int64_t)i * kLevels);
+    const size_t at = ((size_t)lvl * (size_t)P + (size_t)i) * 3;
+    const float* row = acc + 3 * (size_t)t;
+    const float r0 = row[0], r1 = row[1], r2 = row[2];
+    const int rad = radii[i];
+    float l[3] = {lang[at], lang[at + 1], lang[at + 2]};
+    float mm[3] = {m[at], m[at + 1], m[at + 2]};
+    float vv[3] = {v[at], v[at + 1], v[at + 2]};
+    const bool skipped = skip && *skip;
+    float3 d = make_float3(0.f, 0.f, 0.f);
+    if (rad > 0) d = act_lang_backward(l[0], l[1], l[2], r0, r1, r2);
+    if (dlang) {
+        dlang[at] = d.x;
+        dlang[at + 1] = d.y;
+        dlang[at + 2] = d.z;
+    }
+    if (!skipped) {
+        const AdamScalars a = *reinterpret_cast<const AdamScalars*>(step_dev + 1);  // tensor 0
+        adam_one(l[0], d.x, mm[0], vv[0], a);
+        adam_one(l[1], d.y, mm[1], vv[1], a);
+        adam_one(l[2], d.z, mm[2], vv[2], a);
+        lang[at] = l[0];
+        lang[at + 1] = l[1];
+        lang[at + 2] = l[2];
+        m[at] = mm[0];
+        m[at + 1] = mm[1];
+        m[at + 2] = mm[2];
+        v[at] = vv[0];
+        v[at + 1] = vv[1];
+        v[at + 2] = vv[2];
+    }
+    if (!fill_record) return;
+    const float3 f = act_lang(l[0], l[1], l[2]);
+    if (lvl == 0) {  // record[3 i + 2] = {b, f0, f1, f2}: the three language slots, b untouched
+        float* slot = reinterpret_cast<float*>(fill_record + 3 * (size_t)i + 2);
+        slot[1] = f.x;
+        *reinterpret_cast<float2*>(slot + 2) = make_float2(f.y, f.z);
+        return;
+    }
+    if (kLevels > 1) {  // floats 3 (lvl - 1) .. of the Gaussian's kQ quads; the last level pads with zeros
+        float* o = reinterpret_cast<float*>(fill_levels + (size_t)kQ * (size_t)i);
+        o[3 * (lvl - 1)] = f.x;
+        o[3 * (lvl - 1) + 1] = f.y;
+        o[3 * (lvl - 1) + 2] = f.z;
+        if (lvl == kLevels - 1) {
+#pragma unroll
+            for (int e = kE; e < 4 * kQ; e++) o[e] = 0.0f;
+        }
+    }
+}
+
+hipError_t launch_levels_tail(int P, int levels, const int32_t* radii, const float* acc, float* lang, float* exp_avg,
+                              float* exp_avg_sq, float* dlang, const AdamHyper& h, int64_t* step_dev, const int32_t* skip,
+                              float4* fill_record, float4* fill_levels, hipStream_t s)
+{
+    AdamTable tab{};
+    tab.count = 1;
+    tab.hyper[0] = h;
+    tab.step_dev = step_dev;
+    tab.skip = skip;
+    hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(64), 0, s, step_dev, tab);
+    if (P == 0) return hipGetLastError();
+    const int64_t threads = (int64_t)P * levels;
+    const dim3 grid((unsigned)((threads + 255) / 256)), block(256);
+    const int64_t* sd = step_dev;
+#define LSR_TAIL(N) \
+    hipLaunchKernelGGL(k_levels_tail<N>, grid, block, 0, s, P, radii, acc, lang, exp_avg, exp_avg_sq, dlang, sd, skip, \
+                       fill_record, fill_levels)
+    if (levels == 1) LSR_TAIL(1);
+    else if (levels == 2) LSR_TAIL(2);
+    else if (levels == 3) LSR_TAIL(3);
+    else if (levels == 4) LSR_TAIL(4);
+    else return hipErrorInvalidValue;
+#undef LSR_TAIL
+    return hipGetLastError();
+}
+
 // The language step's update at N > 1 (lsr_adam_fill_language): after the gradient all-reduce, the
 // Adam step of the raw feature from its averaged gradient (one tensor; the scalars k_adam_advance
 // formed) and -- as k_language_tail does at N = 1 -- the activated updated feature into the language

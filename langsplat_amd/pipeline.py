@@ -148,6 +148,12 @@ class ViewCache:
         the view it holds is saved, if its counters have arrived (no wait: an event not yet signalled
         skips this visit), it fitted its capacities and the budget allows.  True: `key` has a pack and
         its restore was enqueued in place of the geometry graph."""
+        self.save_pending(r)
+        return self.restore(r, key)
+
+    def save_pending(self, r) -> bool:
+        """visit()'s first half: the view set r holds into a pack, under visit()'s conditions; True if
+        it was saved.  Either way the set's claim is spent."""
         pend, self.pending[r] = self.pending[r], None
         if pend is not None and pend[0] not in self.packs and pend[2].query():
             pkey, ref, _, host = pend
@@ -159,6 +165,12 @@ class ViewCache:
                     self.native.save(r, rendered, pack)
                     self.packs[pkey] = (ref, rendered, pack, nbytes)
                     self.bytes += nbytes
+                    return True
+        return False
+
+    def restore(self, r, key) -> bool:
+        """visit()'s second half: True if `key` has a pack, whose restore into set r was enqueued in
+        place of the geometry graph (counted as a hit, else as a miss)."""
         hit = self.packs.get(key)
         if hit is None:
             self.misses += 1
