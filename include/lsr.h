@@ -923,6 +923,60 @@ int32_t lsr_view_counts(int32_t width, int32_t height, const void* image, uint32
 int32_t lsr_view_save(const lsr_view_args* args, void* stream);
 int32_t lsr_view_restore(const lsr_view_args* args, void* stream);
 
+/* ---- the bound form: a cached view's geometry read in place ---------------------------------------
+ * lsr_view_restore copies a pack (78 MB at 1M Gaussians and 1080p) into the set at every revisit.
+ * The bound form leaves the large arrays where they are.  Every buffer set carries, at the end of its
+ * geometry buffer (lsr_view_bind_layout; lsr_geom_bytes includes both),
+ *   - a table of 32 bytes: { const float4* rec01; const float4* recb; const uint32_t* point_list;
+ *     uint32_t s01, sb; } -- Gaussian i's two leading record words at rec01[s01 i], rec01[s01 i + 1],
+ *     its third word {b, f0, f1, f2} at recb[sb i];
+ *   - a plane of P float4 {b, f0, f1, f2}: the home of the language slots in this form.
+ * A render forward made with LSR_BIND_FORWARD in lsr_forward_args.flags and a lsr_backward made with
+ * LSR_BIND_BACKWARD in lsr_backward_args.flags read the table once per workgroup and gather the
+ * records and the point list through it, so a captured composite + backward bakes the table's
+ * address, not the view's: one capture serves every view.  Without the flags both behave as before.
+ *
+ * Who writes the table and the plane:
+ *   - lsr_forward, LSR_PHASE_GEOMETRY with LSR_BIND_FORWARD (a view without a pack): the preprocess
+ *     writes the identity table (the set's own records at stride 3, its point list, the plane at
+ *     stride 1) and stores b into plane[i].x as well as into the records (lsr_view_save still reads a
+ *     set the geometry phase filled).  LSR_BIND_FORWARD is refused with LSR_PHASE_ALL and by the
+ *     levels entry points.
+ *   - lsr_view_bind with a pack, in place of lsr_view_restore: the table names the pack's rec01
+ *     segment (stride 2), the set's plane and the pack's point list; the pack's b words go into
+ *     plane[i].x; the counters (with lsr_view_restore's re-initialisation rules), ranges, the class
+ *     lists and radii are copied into the set, clamped only with LSR_BIND_CLAMPED (the backward with
+ *     geometry gradients reads it, the language step does not); the fused loss's words, the forward
+ *     flags, the overflow word and *overflow and the backward's class counts are re-initialised as
+ *     lsr_view_restore does.  About 30 MB of traffic at 1M Gaussians and 1080p instead of 157 MB.
+ *     The pack is only read: several sets may be bound to one pack at once, and the caller keeps it
+ *     alive until the last composite / backward of every set bound to it has finished.
+ *   - lsr_view_bind with args->pack == NULL (num_rendered and pack_bytes ignored): the identity
+ *     table, and b from the set's records into plane[i].x, for a set whose geometry phase ran
+ *     without LSR_BIND_FORWARD.
+ *   - the language slots plane[i].yzw: LSR_PHASE_COMPOSITE's fill (with LSR_BIND_FORWARD),
+ *     lsr_fill_language_plane, lsr_adam_fill_language_plane, and a fused update whose
+ *     lsr_backward_args.flags carry LSR_BIND_FILL_PLANE (fill_record is then the plane's address,
+ *     Gaussian i's slots at 16 i + 4, in lsr_backward and in lsr_language_tail alike).  Neither the
+ *     geometry phase nor lsr_view_bind ever writes them.
+ * One launch per lsr_view_bind call on `stream`, no wait.  LSR_ERR_INVALID (message in
+ * lsr_last_error) before any device work for what lsr_view_restore refuses, an unknown bind flag, or
+ * a null geometry buffer (where the table lives).  Added without a change of LSR_ABI_VERSION:
+ * callers detect these entry points by symbol.  The flag values sit above lsr_forward_flags' and
+ * lsr_backward_flags' own. */
+enum lsr_bind_flags {
+    LSR_BIND_FORWARD = 16,     /* lsr_forward_args.flags */
+    LSR_BIND_BACKWARD = 16,    /* lsr_backward_args.flags */
+    LSR_BIND_FILL_PLANE = 32,  /* lsr_backward_args.flags: fill_record is the plane */
+    LSR_BIND_CLAMPED = 1       /* lsr_view_bind's bind_flags */
+};
+int32_t lsr_view_bind_layout(int32_t P, int32_t width, int32_t height, size_t* plane_offset, size_t* table_offset);
+int32_t lsr_view_bind(const lsr_view_args* args, int32_t bind_flags, void* stream);
+int32_t lsr_fill_language_plane(int32_t P, const float* language_feature, int32_t raw, const int32_t* radii, float* plane,
+                                void* stream);
+int32_t lsr_adam_fill_language_plane(const lsr_adam_tensor* tensor, float grad_scale, int64_t* step_dev,
+                                     const int32_t* skip, void* fill_plane, int32_t raw, void* stream);
+
 size_t lsr_masked_l1_scratch_bytes(int32_t C, int64_t HW);
 int32_t lsr_masked_l1_forward(int32_t C, int64_t HW, const float* pred, const float* gt, const void* mask,
                               int32_t mask_is_float, float* loss, void* scratch, void* stream);

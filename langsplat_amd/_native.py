@@ -196,6 +196,12 @@ SIGNATURES = {
     "lsr_view_counts": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_view_save": (ctypes.c_int32, [ctypes.POINTER(LsrViewArgs), _vp]),
     "lsr_view_restore": (ctypes.c_int32, [ctypes.POINTER(LsrViewArgs), _vp]),
+    "lsr_view_bind_layout": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    "lsr_view_bind": (ctypes.c_int32, [ctypes.POINTER(LsrViewArgs), ctypes.c_int32, _vp]),
+    "lsr_fill_language_plane": (ctypes.c_int32, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp]),
+    "lsr_adam_fill_language_plane": (ctypes.c_int32, [ctypes.POINTER(LsrAdamTensor), ctypes.c_float, _vp, _vp, _vp,
+                                                      ctypes.c_int32, _vp]),
     "lsr_fill_language": (ctypes.c_int32, [ctypes.c_int32, _vp, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_adam_step": (ctypes.c_int32, [ctypes.c_int64, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_int64, _vp]),
@@ -227,6 +233,11 @@ SIGNATURES = {
     "lsr_profile_sample": (ctypes.c_int32, [ctypes.c_int32]),
 }
 
+# the bound form of the view cache (include/lsr.h lsr_view_bind): added without an ABI bump, so a
+# library of the same ABI may lack them; has_view_bind() says whether they are there
+OPTIONAL = ("lsr_view_bind_layout", "lsr_view_bind", "lsr_fill_language_plane", "lsr_adam_fill_language_plane")
+BIND_FORWARD, BIND_BACKWARD, BIND_FILL_PLANE, BIND_CLAMPED = 16, 16, 32, 1
+
 _lib: Optional[ctypes.CDLL] = None
 
 
@@ -240,6 +251,8 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         _build.build()
     lib = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -467,6 +480,9 @@ class static_buffers:
 
     def __init__(self):
         self.tensors: Dict[tuple, torch.Tensor] = {}
+        # the bound form (include/lsr.h lsr_view_bind): this set's split-phase forwards and their
+        # backwards read the records and the point list through the set's table
+        self.view_bind = False
 
     @staticmethod
     def active():
@@ -514,8 +530,9 @@ class fused_update:
     _cur = None
 
     def __init__(self, optimizer, param: torch.Tensor, skip: Optional[torch.Tensor] = None, fill: Optional[int] = None,
-                 defer: bool = False):
+                 defer: bool = False, fill_plane: bool = False):
         self.optimizer, self.param, self.skip, self.fill = optimizer, param, skip, fill
+        self.fill_plane = bool(fill_plane)  # fill is a set's plane (LSR_BIND_FILL_PLANE), not its records
         self.defer = bool(defer)
         self.used = False
         self.pending = None  # defer: the deferred tail's arguments (and every tensor they point into)
@@ -663,6 +680,15 @@ def _fill_forward_args(a: LsrForwardArgs, means3D, shs, colors_precomp, language
     a.visible = _ptr(visible)
 
 
+def forward_bound() -> bool:
+    """As this thread's contexts stand, a rasterizer forward is made in the bound form (include/lsr.h
+    LSR_BIND_FORWARD): a split phase in capacity mode into a static_buffers set with view_bind.  The
+    caller of that forward keeps the answer with its backward's state and passes BIND_BACKWARD in the
+    backward's flags (langsplat_amd.rasterizer does, in the autograd context)."""
+    st = static_buffers.active()
+    return st is not None and st.view_bind and forward_phase.active() != 0 and capacity.active() is not None
+
+
 def rasterize_gaussians(rs, means3D, shs, colors_precomp, language_feature, opacities, scales, rotations,
                         cov3D_precomp, raw=0, shs_rest=None, visible=None, loss_target=None, loss_mask=None,
                         out_loss=None, flags=0):
@@ -703,6 +729,8 @@ def rasterize_gaussians(rs, means3D, shs, colors_precomp, language_feature, opac
         a.language_ready = ready.cuda_event
         keep.append(ready)
     a.phase = forward_phase.active()
+    if forward_bound():
+        a.flags |= BIND_FORWARD
     if cap is not None:
         a.capacity_rendered = cap.rendered
         a.capacity_entries = cap.entries
@@ -992,7 +1020,8 @@ def rasterize_gaussians_backward(rs, means3D, shs, colors_precomp, language_feat
     "language_feature_precomp" are computed, the other entries are None (include/lsr.h).
     grad_loss: dL/d(the fused loss of the forward), a () device tensor, or None.  update: a
     fused_update whose Adam step the backward applies to language_feature (include/lsr.h
-    lsr_backward_args.update)."""
+    lsr_backward_args.update).  flags: lsr_backward_flags, and BIND_BACKWARD when the forward was made
+    in the bound form (forward_bound() at the time of the forward)."""
     lib = load()
     device = means3D.device
     P = int(means3D.shape[0])
@@ -1080,6 +1109,8 @@ def rasterize_gaussians_backward(rs, means3D, shs, colors_precomp, language_feat
         update.used = True
         if update.defer:
             a.flags |= BWD_DEFER_TAIL
+        if update.fill is not None and update.fill_plane:
+            a.flags |= BIND_FILL_PLANE
     alloc = _Allocator(device)
     with _on_device(device), alloc:
         _check(lib.lsr_backward(ctypes.byref(s), ctypes.byref(a), _ALLOC_CB, None, _stream(device)), "lsr_backward")
@@ -1113,16 +1144,18 @@ def densification_stats(radii, dmeans2D, max_radii2D=None, xyz_gradient_accum=No
                "lsr_densification_stats")
 
 
-def fill_language(language_feature: torch.Tensor, raw: int, radii: torch.Tensor, record_ptr: int):
+def fill_language(language_feature: torch.Tensor, raw: int, radii: torch.Tensor, record_ptr: int, plane: bool = False):
     """The language slots of a geometry-phase forward's render records from the parameter, on the
-    current stream (include/lsr.h lsr_fill_language)."""
+    current stream (include/lsr.h lsr_fill_language); plane: record_ptr is a bound set's plane
+    (lsr_fill_language_plane)."""
     P = int(radii.shape[0])
     lf = _f32c(language_feature.detach())
     if tuple(lf.shape) != (P, 3) or radii.dtype != torch.int32 or not radii.is_contiguous():
         raise ValueError("fill_language: a (P, 3) feature and the (P,) int32 radii of the same forward")
     with _on_device(lf.device):
-        _check(load().lsr_fill_language(P, _ptr(lf), int(raw), _ptr(radii), ctypes.c_void_p(int(record_ptr)),
-                                        _stream(lf.device)), "lsr_fill_language")
+        fn = load().lsr_fill_language_plane if plane else load().lsr_fill_language
+        _check(fn(P, _ptr(lf), int(raw), _ptr(radii), ctypes.c_void_p(int(record_ptr)), _stream(lf.device)),
+               "lsr_fill_language")
 
 
 def view_pack_bytes(P: int, W: int, H: int, num_rendered: int) -> int:
@@ -1169,6 +1202,28 @@ def view_restore(args: LsrViewArgs, stream: "torch.cuda.Stream"):
     """The pack back into the set in place of its geometry call, enqueued on `stream` (lsr_view_restore)."""
     with _on_device(stream.device):
         _check(load().lsr_view_restore(ctypes.byref(args), _vp(stream.cuda_stream)), "lsr_view_restore")
+
+
+def has_view_bind() -> bool:
+    """The library has the bound form's entry points (include/lsr.h lsr_view_bind)."""
+    lib = load()
+    return all(hasattr(lib, n) for n in OPTIONAL)
+
+
+def view_bind_layout(P: int, W: int, H: int) -> Dict[str, int]:
+    """Byte offsets of a set's plane and table in its geometry buffer (lsr_view_bind_layout)."""
+    plane, table = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _check(load().lsr_view_bind_layout(int(P), int(W), int(H), ctypes.byref(plane), ctypes.byref(table)),
+           "lsr_view_bind_layout")
+    return {"plane": int(plane.value), "table": int(table.value)}
+
+
+def view_bind(args: LsrViewArgs, stream: "torch.cuda.Stream", clamped: bool = False):
+    """The set bound to args' pack (args.pack None: to its own arrays) in place of its geometry call or a
+    restore, enqueued on `stream` (include/lsr.h lsr_view_bind)."""
+    with _on_device(stream.device):
+        _check(load().lsr_view_bind(ctypes.byref(args), BIND_CLAMPED if clamped else 0, _vp(stream.cuda_stream)),
+               "lsr_view_bind")
 
 
 def mark_visible(means3D, viewmatrix, projmatrix):

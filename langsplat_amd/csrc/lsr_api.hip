@@ -316,6 +316,7 @@ static int32_t render_forward_and_finish(const lsr_settings* s, const lsr_forwar
     rp.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
     rp.cover = reinterpret_cast<uint8_t*>(binning + L.cover);
     rp.record = reinterpret_cast<const float4*>(geom + L.record);
+    if (a->flags & LSR_BIND_FORWARD) rp.bind = reinterpret_cast<const ViewBind*>(geom + L.view_bind);
     rp.bg = s->bg;
     rp.final_T = reinterpret_cast<float*>(image + L.final_T);
     rp.n_contrib = reinterpret_cast<uint32_t*>(image + L.n_contrib);
@@ -443,8 +444,11 @@ static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, ls
         return fail(LSR_ERR_INVALID, "lsr_forward: settings tensors missing");
     if (a->raw & ~(LSR_RAW_OPACITY | LSR_RAW_SCALES | LSR_RAW_ROTATIONS | LSR_RAW_LANGUAGE))
         return fail(LSR_ERR_INVALID, "lsr_forward: unknown raw flag");
-    if (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD))
+    if (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD | LSR_BIND_FORWARD))
         return fail(LSR_ERR_INVALID, "lsr_forward: unknown flag");
+    const bool bound = (a->flags & LSR_BIND_FORWARD) != 0;
+    if (bound && (a->phase == LSR_PHASE_ALL || lv))
+        return fail(LSR_ERR_INVALID, "lsr_forward: LSR_BIND_FORWARD needs a forward phase (capacity mode) of lsr_forward");
     if (a->shs_rest && (!a->shs || a->M < 2))
         return fail(LSR_ERR_INVALID, "lsr_forward: shs_rest needs shs (features_dc) and M >= 2");
     if (a->capacity_rendered < 0 || (a->capacity_rendered > 0 && a->capacity_entries <= 0) ||
@@ -562,11 +566,25 @@ static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, ls
         *num_rendered = R_cap;
         if (deferred && a->phase == LSR_PHASE_COMPOSITE) {
             LSR_TRY(launch_fill_language(P, a->language_feature, a->raw, a->radii,
-                                         reinterpret_cast<float4*>(geom + L.record), stream),
+                                         reinterpret_cast<float4*>(geom + (bound ? L.lang_plane : L.record)), stream,
+                                         bound ? 1 : 0),
                     "fill language");
             if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
         }
         return render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
+    }
+    // the bound form's geometry phase (a cache miss): b into the plane and the identity table by the
+    // preprocess, which needs the point list's address: the binning buffer is taken first
+    char* bound_binning = nullptr;
+    if (bound) {
+        const int64_t E_cap = !depth_order_uses_pass_count(P) ? std::min<int64_t>(a->capacity_entries, L.fused_cap)
+                                                                : a->capacity_entries;
+        const Layout Lc = make_layout(P, W, H, a->capacity_rendered, E_cap);
+        bound_binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, Lc.binning_bytes));
+        if (!bound_binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
+        pp.plane = reinterpret_cast<float4*>(geom + L.lang_plane);
+        pp.bind = reinterpret_cast<ViewBind*>(geom + L.view_bind);
+        pp.bind_point_list = reinterpret_cast<const uint32_t*>(bound_binning + Lc.point_list);
     }
     LSR_TRY(launch_preprocess(pp, stream), "preprocess");
     hm.mark();
@@ -598,7 +616,7 @@ static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, ls
                                    (uint32_t)E_cap, placed),
                 "depth order");
         L = make_layout(P, W, H, R_cap, E_cap);
-        char* binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, L.binning_bytes));
+        char* binning = bound_binning ? bound_binning : static_cast<char*>(alloc(user, LSR_BUF_BINNING, L.binning_bytes));
         if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
         LSR_TRY(launch_binning(P, R_cap, L, geom, image, binning, &hb->stall, stream, debug, fused,
                                DevCount{counters + kCntSuper, counters + kCntOverflow}, placed),
@@ -914,8 +932,11 @@ int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_allo
     }
     if (a->raw & ~(LSR_RAW_OPACITY | LSR_RAW_SCALES | LSR_RAW_ROTATIONS | LSR_RAW_LANGUAGE))
         return fail(LSR_ERR_INVALID, "lsr_backward: unknown raw flag");
-    if (a->flags & ~(LSR_BWD_RECORDS_ZEROED | LSR_BWD_SHARED_CU | LSR_BWD_DEFER_TAIL))
+    if (a->flags & ~(LSR_BWD_RECORDS_ZEROED | LSR_BWD_SHARED_CU | LSR_BWD_DEFER_TAIL | LSR_BIND_BACKWARD |
+                     LSR_BIND_FILL_PLANE))
         return fail(LSR_ERR_INVALID, "lsr_backward: unknown flag");
+    if ((a->flags & LSR_BIND_FILL_PLANE) && !a->fill_record)
+        return fail(LSR_ERR_INVALID, "lsr_backward: LSR_BIND_FILL_PLANE needs fill_record (the plane)");
     const bool defer = (a->flags & LSR_BWD_DEFER_TAIL) != 0;
     if (defer && !a->update) return fail(LSR_ERR_INVALID, "lsr_backward: LSR_BWD_DEFER_TAIL needs update");
     if (geometry && a->shs_rest && (!a->shs || a->M < 2 || !a->dL_dsh_rest))
@@ -987,6 +1008,7 @@ int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_allo
     rp.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
     rp.cover = reinterpret_cast<uint8_t*>(binning + L.cover);
     rp.record = reinterpret_cast<const float4*>(geom + L.record);
+    if (a->flags & LSR_BIND_BACKWARD) rp.bind = reinterpret_cast<const ViewBind*>(geom + L.view_bind);
     rp.bg = s->bg;
     rp.final_T = reinterpret_cast<float*>(image + L.final_T);
     rp.n_contrib = reinterpret_cast<uint32_t*>(image + L.n_contrib);
@@ -1022,7 +1044,8 @@ int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_allo
         AdamHyper h{u.lr, u.beta1, u.beta2, u.eps, u.step};
         LSR_TRY(launch_language_tail(P, a->radii, grad, const_cast<float*>(a->language_feature), u.exp_avg, u.exp_avg_sq,
                                      a->dL_dmeans2D, a->dL_dlanguage_feature, h, a->update_step_dev, a->update_skip,
-                                     reinterpret_cast<float4*>(a->fill_record), 0, stream),
+                                     reinterpret_cast<float4*>(a->fill_record), 0, stream,
+                                     (a->flags & LSR_BIND_FILL_PLANE) ? 1 : 0),
                 "language tail");
         return LSR_OK;
     }
@@ -1147,6 +1170,65 @@ static int32_t view_copy(const lsr_view_args* a, void* stream_ptr, bool restore)
 }
 
 int32_t lsr_view_save(const lsr_view_args* a, void* stream) { return view_copy(a, stream, false); }
+
+int32_t lsr_view_bind_layout(int32_t P, int32_t width, int32_t height, size_t* plane, size_t* table)
+{
+    if (P < 0 || width < 0 || height < 0 || !plane || !table)
+        return fail(LSR_ERR_INVALID, "lsr_view_bind_layout: invalid argument");
+    const Layout L = make_layout(P, width, height, 0, 0);
+    *plane = L.lang_plane;
+    *table = L.view_bind;
+    return LSR_OK;
+}
+
+int32_t lsr_view_bind(const lsr_view_args* a, int32_t bind_flags, void* stream_ptr)
+{
+    auto bad = [&](const char* what) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "lsr_view_bind: %s", what);
+        return fail(LSR_ERR_INVALID, msg);
+    };
+    if (!a) return bad("null argument");
+    if (bind_flags & ~LSR_BIND_CLAMPED) return bad("unknown bind flag");
+    if (a->P < 1 || a->width < 1 || a->height < 1 || a->width > 65535 * kTile || a->height > 65535 * kTile)
+        return bad("P, width and height must be positive");
+    if (a->capacity_rendered < 1 || a->capacity_entries < 1 || a->capacity_rendered > 0xFFFFFFFFll ||
+        a->capacity_entries > 0xFFFFFFFFll)
+        return bad("the capacities must be positive (both < 2^32)");
+    if (!a->geom || !a->image || !a->binning || !a->radii)
+        return bad("null buffer (the set's table and plane live in its geometry buffer)");
+    if (a->pack) {
+        if (a->num_rendered < 0 || a->num_rendered > a->capacity_rendered)
+            return bad("num_rendered must be 0 .. capacity_rendered");
+        if (a->pack_bytes < lsr_view_pack_bytes(a->P, a->width, a->height, a->num_rendered))
+            return bad("pack_bytes is below lsr_view_pack_bytes");
+    }
+    if (((reinterpret_cast<uintptr_t>(a->geom) | reinterpret_cast<uintptr_t>(a->image) |
+          reinterpret_cast<uintptr_t>(a->binning) | reinterpret_cast<uintptr_t>(a->pack)) & 15) != 0 ||
+        (reinterpret_cast<uintptr_t>(a->radii) & 3) != 0)
+        return bad("the buffers and the pack must be 16-byte aligned");
+    if (a->reserved != 0 || (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD)))
+        return bad("unknown flag");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    ViewParams v{};
+    v.P = a->P;
+    v.W = a->width;
+    v.H = a->height;
+    v.R_cap = a->capacity_rendered;
+    v.R = a->pack ? a->num_rendered : 0;
+    v.geom = static_cast<char*>(a->geom);
+    v.image = static_cast<char*>(a->image);
+    v.binning = static_cast<char*>(a->binning);
+    v.pack = static_cast<char*>(a->pack);
+    v.radii = a->radii;
+    v.overflow = a->pack ? a->overflow : nullptr;
+    v.fwd_flags = ((a->flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) |
+                  (a->fused_loss ? kFwdFusedLoss : 0u) | ((a->flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) |
+                  ((a->flags & LSR_FWD_NO_BACKWARD) ? kFwdNoBackward : 0u);
+    LSR_TRY(launch_view_bind(v, (bind_flags & LSR_BIND_CLAMPED) != 0, stream), "view bind");
+    return LSR_OK;
+}
 
 int32_t lsr_view_restore(const lsr_view_args* a, void* stream) { return view_copy(a, stream, true); }
 
@@ -1373,17 +1455,29 @@ int32_t lsr_mark_visible(int32_t P, const float* means3D, const float* viewmatri
     return LSR_OK;
 }
 
-int32_t lsr_fill_language(int32_t P, const float* language_feature, int32_t raw, const int32_t* radii, float* record,
-                          void* stream_ptr)
+static int32_t fill_language(int32_t P, const float* language_feature, int32_t raw, const int32_t* radii, float* record,
+                             void* stream_ptr, int plane)
 {
     if (P < 0 || (P > 0 && (!language_feature || !radii || !record)) ||
         (reinterpret_cast<uintptr_t>(record) & 15) != 0)
-        return fail(LSR_ERR_INVALID, "lsr_fill_language: invalid argument");
+        return fail(LSR_ERR_INVALID, plane ? "lsr_fill_language_plane: invalid argument" : "lsr_fill_language: invalid argument");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
     const bool debug = false;
-    LSR_TRY(launch_fill_language(P, language_feature, raw, radii, reinterpret_cast<float4*>(record), stream),
+    LSR_TRY(launch_fill_language(P, language_feature, raw, radii, reinterpret_cast<float4*>(record), stream, plane),
             "fill language");
     return LSR_OK;
+}
+
+int32_t lsr_fill_language(int32_t P, const float* language_feature, int32_t raw, const int32_t* radii, float* record,
+                          void* stream)
+{
+    return fill_language(P, language_feature, raw, radii, record, stream, 0);
+}
+
+int32_t lsr_fill_language_plane(int32_t P, const float* language_feature, int32_t raw, const int32_t* radii, float* plane,
+                                void* stream)
+{
+    return fill_language(P, language_feature, raw, radii, plane, stream, 1);
 }
 
 // planes / H / W >= 1 and a grid that fits: nullptr, or what is wrong
@@ -1522,8 +1616,23 @@ int32_t lsr_adam_multi(int32_t count, const lsr_adam_tensor* tensors, float grad
     return LSR_OK;
 }
 
+static int32_t adam_fill_language(const lsr_adam_tensor* t, float grad_scale, int64_t* step_dev, const int32_t* skip,
+                                  void* fill_record, int32_t raw, void* stream_ptr, int plane);
+
 int32_t lsr_adam_fill_language(const lsr_adam_tensor* t, float grad_scale, int64_t* step_dev, const int32_t* skip,
-                               void* fill_record, int32_t raw, void* stream_ptr)
+                               void* fill_record, int32_t raw, void* stream)
+{
+    return adam_fill_language(t, grad_scale, step_dev, skip, fill_record, raw, stream, 0);
+}
+
+int32_t lsr_adam_fill_language_plane(const lsr_adam_tensor* t, float grad_scale, int64_t* step_dev, const int32_t* skip,
+                                     void* fill_plane, int32_t raw, void* stream)
+{
+    return adam_fill_language(t, grad_scale, step_dev, skip, fill_plane, raw, stream, 1);
+}
+
+static int32_t adam_fill_language(const lsr_adam_tensor* t, float grad_scale, int64_t* step_dev, const int32_t* skip,
+                                  void* fill_record, int32_t raw, void* stream_ptr, int plane)
 {
     if (!t || !step_dev || !fill_record || t->n < 0 || t->n % 3 != 0 || t->n / 3 > INT32_MAX ||
         (t->n > 0 && (!t->param || !t->grad || !t->exp_avg || !t->exp_avg_sq)) ||
@@ -1535,7 +1644,7 @@ int32_t lsr_adam_fill_language(const lsr_adam_tensor* t, float grad_scale, int64
     const bool debug = false;
     const AdamHyper h{t->lr, t->beta1, t->beta2, t->eps, t->step};
     LSR_TRY(launch_adam_fill((int)(t->n / 3), t->grad, grad_scale, t->param, t->exp_avg, t->exp_avg_sq, h, step_dev,
-                             skip, reinterpret_cast<float4*>(fill_record), raw, stream),
+                             skip, reinterpret_cast<float4*>(fill_record), raw, stream, plane),
             "adam fill");
     return LSR_OK;
 }
@@ -1563,7 +1672,8 @@ int32_t lsr_language_tail(const lsr_settings* s, const lsr_backward_args* a, voi
     const int32_t* skip = P > 0 ? reinterpret_cast<const int32_t*>(grad + 3 * (size_t)P) : a->update_skip;
     LSR_TRY(launch_language_tail(P, a->radii, grad, const_cast<float*>(a->language_feature), u.exp_avg, u.exp_avg_sq,
                                  a->dL_dmeans2D, a->dL_dlanguage_feature, h, a->update_step_dev, skip,
-                                 reinterpret_cast<float4*>(a->fill_record), 1, stream),
+                                 reinterpret_cast<float4*>(a->fill_record), 1, stream,
+                                 (a->flags & LSR_BIND_FILL_PLANE) ? 1 : 0),
             "language tail");
     return LSR_OK;
 }

@@ -73,6 +73,19 @@ constexpr size_t kSupWords = sup_words(512);  // the allocation (either bucket c
 size_t scan_region_words(int64_t n);  // look-back status + ticket of one scan of n words
 constexpr int kDepthScans = 5;         // 4 depth-sort passes + the instance-offset scan
 
+// Where the render kernels of a bound buffer set (lsr_view_bind) find the arrays a view pack also
+// holds, read once per workgroup from the set's table (Layout::view_bind): the captured graphs bake
+// the table's address, so one captured composite + backward serves every view.  Gaussian i's two
+// leading record words are rec01[s01 i], rec01[s01 i + 1] (the set's records: s01 = 3; a pack's rec01
+// segment: 2), its third word {b, f0, f1, f2} is recb[sb i] (the set's records: 3; the plane: 1).
+struct ViewBind {
+    const float4* rec01;
+    const float4* recb;
+    const uint32_t* point_list;
+    uint32_t s01, sb;
+};
+static_assert(sizeof(ViewBind) == 32, "two 16-byte words");
+
 struct Layout {
     // geometry (per Gaussian)
     size_t depth_key, tiles_touched, rect, record, clamped, sorted_ids, super_offset;
@@ -96,6 +109,10 @@ struct Layout {
     size_t sup_status;
     size_t grad_records;      // P x kGradStrideLang floats: the language step's gradient records (cleared
                               // by the render forward under LSR_FWD_ZERO_GRAD_RECORDS)
+    // the bound form of the view cache (lsr_view_bind): a compact plane of {b, f0, f1, f2} per Gaussian,
+    // the home of the language slots there, and the set's ViewBind table.  Last in the buffer: no
+    // other offset moved when they were added
+    size_t lang_plane, view_bind;
     size_t geom_bytes;
     // image (per pixel / tile)
     size_t counters, ranges, final_T, n_contrib, tile_lists, loss_partial, loss_code;
@@ -165,6 +182,8 @@ inline Layout make_layout(int P, int W, int H, int64_t R, int64_t E)
     L.fused_keys = take(4 * (size_t)L.fused_cap);
     L.fused_vals = take(4 * (size_t)L.fused_cap);
     L.pre_partial = take(16 * ((p + kPreThreads - 1) / kPreThreads));
+    L.lang_plane = take(16 * p);
+    L.view_bind = take(sizeof(ViewBind));
     L.geom_bytes = o;
 
     L.gx = (W + kTile - 1) / kTile;
@@ -236,6 +255,11 @@ struct PreprocessParams {
     const float* shs_rest;    // split SH rows (shs = dc only) or null
     uint8_t* visible;         // optional radii > 0 bytes
     int lang_deferred;        // the records' language slots are filled later (launch_fill_language)
+    // the bound form (LSR_BIND_FORWARD): b also into plane[i].x, and the first thread writes the
+    // identity table (the set's own arrays) into *bind; both null: off
+    float4* plane;
+    ViewBind* bind;
+    const uint32_t* bind_point_list;
 };
 
 struct PreprocessBwdParams {
@@ -259,6 +283,9 @@ struct RenderParams {
     // by the forward for every instance it loads and read by the backward instead of recomputing it
     uint8_t* cover;
     const float4* record;
+    // non-null: rec01 / recb / point_list come from this table instead (bound_view, lsr_render.hip);
+    // k_render_forward and k_render_backward only
+    const ViewBind* bind;
     const float* bg;
     float* final_T;
     uint32_t* n_contrib;
@@ -306,8 +333,9 @@ struct RenderParams {
 
 hipError_t launch_preprocess(const PreprocessParams& p, hipStream_t s);
 // the language slots of the visible Gaussians' records (after a deferred preprocess)
+// plane: `record` is a compact plane, Gaussian i's slots in record[i] (else in record[3 i + 2])
 hipError_t launch_fill_language(int P, const float* lang, int raw, const int32_t* radii, float4* record,
-                                hipStream_t s);
+                                hipStream_t s, int plane = 0);
 hipError_t launch_preprocess_backward(const PreprocessBwdParams& p, hipStream_t s);
 hipError_t launch_grad_epilogue(int P, const int* radii, const float* grad, int stride, const float* lang,
                                 int raw_lang, float* dmeans2D, float* dlang, hipStream_t s);
@@ -419,7 +447,7 @@ hipError_t launch_adam_multi(AdamTable& tab, float grad_scale, hipStream_t s);
 // culled may carry another view's partials)
 hipError_t launch_language_tail(int P, const int32_t* radii, const float* grad, float* lang, float* exp_avg,
                                 float* exp_avg_sq, float* dmeans2D, float* dlang, const AdamHyper& h, int64_t* step_dev,
-                                const int32_t* skip, float4* fill, int deferred, hipStream_t s);
+                                const int32_t* skip, float4* fill, int deferred, hipStream_t s, int fill_plane = 0);
 // lsr_levels_step_backward with update: k_adam_advance (one tensor, the skip flag), then one pass per
 // (Gaussian, level): k_levels_grad_epilogue's gradient from acc (P rows of 3 levels floats) and the raw
 // features lang (levels x P x 3) into dlang (may be null), the Adam step of lang and its moments
@@ -430,7 +458,7 @@ hipError_t launch_levels_tail(int P, int levels, const int32_t* radii, const flo
                               float4* fill_record, float4* fill_levels, hipStream_t s);
 hipError_t launch_adam_fill(int P, const float* grad, float grad_scale, float* lang, float* exp_avg, float* exp_avg_sq,
                             const AdamHyper& h, int64_t* step_dev, const int32_t* skip, float4* fill, int raw,
-                            hipStream_t s);
+                            hipStream_t s, int fill_plane = 0);
 // zero `bytes` bytes at p with a kernel (no memset node in a captured graph)
 hipError_t zero_fill(void* p, size_t bytes, hipStream_t s);
 hipError_t launch_densification_stats(int P, const int* radii, const float* dmeans2D, float* max_radii, float* accum,
@@ -529,6 +557,13 @@ struct ViewParams {
 // one launch: the set's kept state into the pack, or (restore) back, with the words the geometry phase
 // clears on every run
 hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s);
+// lsr_view_bind: the set's table and the small per-view state, one launch.  v.pack set (a hit): the
+// table names the pack's rec01 and point_list and the set's plane; counters (k_view_copy<true>'s
+// rules), ranges, class lists, radii and -- clamped set -- clamped are copied, recb goes into
+// plane[i].x, the loss words are cleared.  v.pack null (a miss, after the geometry phase): the table
+// names the set's own arrays, and b goes from the records into plane[i].x.  Never writes plane[i].yzw
+// or the pack.
+hipError_t launch_view_bind(const ViewParams& v, bool clamped, hipStream_t s);
 // counters[0..8) of an image buffer into pinned host memory (system-scope stores, as k_publish_counters)
 hipError_t launch_view_counts(const uint32_t* counters, uint32_t* host, hipStream_t s);
 

@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void k_language_tail(int P, const int32_t* __r
                                                        float* __restrict__ dmeans2D, float* __restrict__ dlang,
                                                        const int64_t* __restrict__ step_dev,
                                                        const int32_t* __restrict__ skip, float4* __restrict__ fill,
-                                                       int deferred)
+                                                       int deferred, int fill_plane)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
@@ -208,9 +208,9 @@ __global__ __launch_bounds__(256) void k_language_tail(int P, const int32_t* __r
         v[i3 + 1] = vv[1];
         v[i3 + 2] = vv[2];
     }
-    if (fill) {  // record[3 i + 2] = {b, f0, f1, f2}: the three language slots, b untouched
+    if (fill) {  // record[3 i + 2] (fill_plane: plane[i]) = {b, f0, f1, f2}: the three language slots, b untouched
         const float3 f = act_lang(l[0], l[1], l[2]);
-        float* slot = reinterpret_cast<float*>(fill + 3 * (size_t)i + 2);
+        float* slot = reinterpret_cast<float*>(fill_plane ? fill + i : fill + 3 * (size_t)i + 2);
         slot[1] = f.x;
         *reinterpret_cast<float2*>(slot + 2) = make_float2(f.y, f.z);
     }
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void k_language_tail(int P, const int32_t* __r
 
 hipError_t launch_language_tail(int P, const int32_t* radii, const float* grad, float* lang, float* exp_avg,
                                 float* exp_avg_sq, float* dmeans2D, float* dlang, const AdamHyper& h, int64_t* step_dev,
-                                const int32_t* skip, float4* fill, int deferred, hipStream_t s)
+                                const int32_t* skip, float4* fill, int deferred, hipStream_t s, int fill_plane)
 {
     AdamTable tab{};
     tab.count = 1;
@@ -228,7 +228,7 @@ hipError_t launch_language_tail(int P, const int32_t* radii, const float* grad, 
     hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(64), 0, s, step_dev, tab);
     if (P == 0) return hipGetLastError();
     hipLaunchKernelGGL(k_language_tail, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, radii, grad, lang,
-                       exp_avg, exp_avg_sq, dmeans2D, dlang, (const int64_t*)step_dev, skip, fill, deferred);
+                       exp_avg, exp_avg_sq, dmeans2D, dlang, (const int64_t*)step_dev, skip, fill, deferred, fill_plane);
     return hipGetLastError();
 }
 
@@ -342,7 +342,8 @@ hipError_t launch_levels_tail(int P, int levels, const int32_t* radii, const flo
 __global__ __launch_bounds__(256) void k_adam_fill(int P, const float* __restrict__ grad, float grad_scale,
                                                    float* __restrict__ lang, float* __restrict__ m,
                                                    float* __restrict__ v, const int64_t* __restrict__ step_dev,
-                                                   const int32_t* __restrict__ skip, float4* __restrict__ fill, int raw)
+                                                   const int32_t* __restrict__ skip, float4* __restrict__ fill, int raw,
+                                                   int fill_plane)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
@@ -363,14 +364,14 @@ __global__ __launch_bounds__(256) void k_adam_fill(int P, const float* __restric
     }
     float3 f = make_float3(l[0], l[1], l[2]);
     if (raw & LSR_RAW_LANGUAGE) f = act_lang(l[0], l[1], l[2]);
-    float* slot = reinterpret_cast<float*>(fill + 3 * (size_t)i + 2);  // {b, f0, f1, f2}, b untouched
+    float* slot = reinterpret_cast<float*>(fill_plane ? fill + i : fill + 3 * (size_t)i + 2);  // {b, f0, f1, f2}, b untouched
     slot[1] = f.x;
     *reinterpret_cast<float2*>(slot + 2) = make_float2(f.y, f.z);
 }
 
 hipError_t launch_adam_fill(int P, const float* grad, float grad_scale, float* lang, float* exp_avg, float* exp_avg_sq,
                             const AdamHyper& h, int64_t* step_dev, const int32_t* skip, float4* fill, int raw,
-                            hipStream_t s)
+                            hipStream_t s, int fill_plane)
 {
     AdamTable tab{};
     tab.count = 1;
@@ -380,7 +381,7 @@ hipError_t launch_adam_fill(int P, const float* grad, float grad_scale, float* l
     hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(64), 0, s, step_dev, tab);
     if (P == 0) return hipGetLastError();
     hipLaunchKernelGGL(k_adam_fill, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, P, grad, grad_scale, lang,
-                       exp_avg, exp_avg_sq, (const int64_t*)step_dev, skip, fill, raw);
+                       exp_avg, exp_avg_sq, (const int64_t*)step_dev, skip, fill, raw, fill_plane);
     return hipGetLastError();
 }
 

@@ -168,6 +168,15 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(PreprocessParams p)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     for (int w = i; w < p.zero_words; w += gridDim.x * blockDim.x) p.zero[w] = 0u;
     for (int w = i; w < p.zero2_words; w += gridDim.x * blockDim.x) p.zero2[w] = 0u;
+    if (p.bind && i == 0) {  // the bound form, a cache miss: the table names the set's own arrays
+        ViewBind t;
+        t.rec01 = p.record;
+        t.recb = p.plane;
+        t.point_list = p.bind_point_list;
+        t.s01 = 3u;
+        t.sb = 1u;
+        *p.bind = t;
+    }
     // Per-Gaussian inputs are loaded first, so their latency overlaps the SH staging below
     // (issued after the barrier they would add a second memory round trip to every block).
     const bool live = i < p.P;
@@ -358,6 +367,8 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(PreprocessParams p)
         reinterpret_cast<float*>(rec + 2)[0] = rgb[2];  // LSR_PHASE_COMPOSITE_FILLED); b only
     else
         rec[2] = make_float4(rgb[2], f0, f1, f2);
+    // the bound form: b also where the compositing reads it (the plane's language slots are the fill's)
+    if (p.plane) reinterpret_cast<float*>(p.plane + i)[0] = rgb[2];
     my_tiles = area;
     my_supers = (uint32_t)(((r4[2] + kSuper - 1) / kSuper - r4[0] / kSuper) *
                            ((r4[3] + kSuper - 1) / kSuper - r4[1] / kSuper));
@@ -411,7 +422,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(PreprocessParams p)
 // Gaussians per thread: their 48 feature bytes and 16 radius bytes are whole dwordx4 loads (a wave
 // reads 3 KB + 1 KB contiguous); each record gets its three slots only (a dword and a dwordx2 store,
 // no read of the colour word b).  On the pipelined step's critical path.
-__device__ __forceinline__ void fill_one(float4* record, size_t i, float f0, float f1, float f2, int raw)
+__device__ __forceinline__ void fill_one(float4* record, size_t i, float f0, float f1, float f2, int raw, int plane)
 {
     if (raw & LSR_RAW_LANGUAGE) {
         const float3 f = act_lang(f0, f1, f2);
@@ -419,13 +430,14 @@ __device__ __forceinline__ void fill_one(float4* record, size_t i, float f0, flo
         f1 = f.y;
         f2 = f.z;
     }
-    float* r = reinterpret_cast<float*>(record + 3 * i + 2);
+    float* r = reinterpret_cast<float*>(plane ? record + i : record + 3 * i + 2);
     r[1] = f0;
     *reinterpret_cast<float2*>(r + 2) = make_float2(f1, f2);
 }
 
 __global__ __launch_bounds__(256) void k_fill_language(int P, const float* __restrict__ lang, int raw,
-                                                       const int32_t* __restrict__ radii, float4* __restrict__ record)
+                                                       const int32_t* __restrict__ radii, float4* __restrict__ record,
+                                                       int plane)
 {
     const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;  // Gaussians 4 q .. 4 q + 3
     const int64_t i0 = 4 * q;
@@ -435,23 +447,23 @@ __global__ __launch_bounds__(256) void k_fill_language(int P, const float* __res
         const int4 r = reinterpret_cast<const int4*>(radii)[q];
         const float4* l4 = reinterpret_cast<const float4*>(lang) + 3 * q;
         const float4 a = l4[0], b = l4[1], c = l4[2];  // {f0 f1 f2 | f0} {f1 f2 | f0 f1} {f2 | f0 f1 f2}
-        if (r.x > 0) fill_one(record, (size_t)i0, a.x, a.y, a.z, raw);
-        if (r.y > 0) fill_one(record, (size_t)i0 + 1, a.w, b.x, b.y, raw);
-        if (r.z > 0) fill_one(record, (size_t)i0 + 2, b.z, b.w, c.x, raw);
-        if (r.w > 0) fill_one(record, (size_t)i0 + 3, c.y, c.z, c.w, raw);
+        if (r.x > 0) fill_one(record, (size_t)i0, a.x, a.y, a.z, raw, plane);
+        if (r.y > 0) fill_one(record, (size_t)i0 + 1, a.w, b.x, b.y, raw, plane);
+        if (r.z > 0) fill_one(record, (size_t)i0 + 2, b.z, b.w, c.x, raw, plane);
+        if (r.w > 0) fill_one(record, (size_t)i0 + 3, c.y, c.z, c.w, raw, plane);
         return;
     }
     for (int64_t i = i0; i < P && i < i0 + 4; i++)
-        if (radii[i] > 0) fill_one(record, (size_t)i, lang[3 * i], lang[3 * i + 1], lang[3 * i + 2], raw);
+        if (radii[i] > 0) fill_one(record, (size_t)i, lang[3 * i], lang[3 * i + 1], lang[3 * i + 2], raw, plane);
 }
 
 hipError_t launch_fill_language(int P, const float* lang, int raw, const int32_t* radii, float4* record,
-                                hipStream_t s)
+                                hipStream_t s, int plane)
 {
     if (P == 0) return hipSuccess;
     const int64_t threads = ((int64_t)P + 3) / 4;
     hipLaunchKernelGGL(k_fill_language, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, P, lang, raw, radii,
-                       record);
+                       record, plane);
     return hipGetLastError();
 }
 

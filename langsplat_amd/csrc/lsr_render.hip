@@ -431,6 +431,46 @@ __device__ __forceinline__ void loss_block_partial(const RenderParams& p, float 
     if (threadIdx.x == 0) p.loss_partial[blockIdx.x] = t;
 }
 
+// Where this launch finds the records and the point list: the arguments' own arrays, or (p.bind, a
+// buffer set bound by lsr_view_bind) what the set's table names -- a view pack read in place.  The
+// table is read through the constant address space: a uniform address there is a scalar load, which
+// the compiler may issue again where it needs a value (as it does for kernel arguments) instead of
+// holding five more values across the walk.  (An earlier launch wrote the table; the scalar cache
+// starts clean at every kernel, which is what makes arguments' pointees readable that way too.)
+// The pointers it yields are marked global: a pointer loaded from memory is otherwise a flat one,
+// whose loads also count against the LDS counter.
+#define LSR_GLOBAL __attribute__((address_space(1)))
+#define LSR_CONSTANT __attribute__((address_space(4)))
+struct BoundView {
+    LSR_GLOBAL const float4* rec01;
+    LSR_GLOBAL const float4* recb;
+    LSR_GLOBAL const uint32_t* point_list;
+    uint32_t s01, sb;
+    // Gaussian g's record words: {x, y, conic.x, conic.y}, {conic.z, opacity, r, g}, {b, f0, f1, f2}
+    // (float4 is a class type, which cannot be copied out of an address space: the element's address
+    // goes back to a generic pointer, and the compiler still knows where it came from)
+    __device__ __forceinline__ float4 word01(uint32_t g, int w) const { return *(const float4*)&rec01[(size_t)s01 * g + w]; }
+    __device__ __forceinline__ float4 word2(uint32_t g) const { return *(const float4*)&recb[(size_t)sb * g]; }
+};
+__device__ __forceinline__ BoundView bound_view(const RenderParams& p)
+{
+    BoundView v;
+    if (!p.bind) {
+        v.rec01 = (LSR_GLOBAL const float4*)p.record;
+        v.recb = (LSR_GLOBAL const float4*)(p.record + 2);
+        v.point_list = (LSR_GLOBAL const uint32_t*)p.point_list;
+        v.s01 = v.sb = 3u;
+        return v;
+    }
+    const LSR_CONSTANT ViewBind* t = (const LSR_CONSTANT ViewBind*)p.bind;
+    v.rec01 = (LSR_GLOBAL const float4*)t->rec01;
+    v.recb = (LSR_GLOBAL const float4*)t->recb;
+    v.point_list = (LSR_GLOBAL const uint32_t*)t->point_list;
+    v.s01 = t->s01;
+    v.sb = t->sb;
+    return v;
+}
+
 // The language feature of one pixel composited by a scalar front-to-back walk over the whole tile
 // list, reading the records from global memory: the oracle's render_pixel with the main walk's
 // cutoff test (power < cut rejects exactly what alpha < 1/255 would), so the same operations and the
@@ -440,9 +480,10 @@ __device__ void composite_lang_pixel(const RenderParams& p, uint2 range, float p
 {
     float T = 1.0f;
     f0 = f1 = f2 = 0.0f;
+    const BoundView v = bound_view(p);
     for (uint32_t k = range.x; k < range.y; k++) {
-        const uint32_t g = p.point_list[k];
-        const float4 a = p.record[3 * (size_t)g], b = p.record[3 * (size_t)g + 1], c = p.record[3 * (size_t)g + 2];
+        const uint32_t g = v.point_list[k];
+        const float4 a = v.word01(g, 0), b = v.word01(g, 1), c = v.word2(g);
         const float dx = a.x - pfx, dy = a.y - pfy;
         const float hx = -0.5f * a.z, hz = -0.5f * b.x;
         const float pw = fma_(dx, fma_(-a.w, dy, hx * dx), (hz * dy) * dy);
@@ -670,7 +711,8 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
     // a batch's point_list ids are loaded during the previous batch's walk, so its load phase waits
     // for one memory round trip (the record gather), not two
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a, c = a;
-    uint32_t g_next = start + t < end ? p.point_list[start + t] : 0u;
+    const BoundView vb = bound_view(p);  // (the load phase only: ids, record gather)
+    uint32_t g_next = start + t < end ? vb.point_list[start + t] : 0u;
     for (uint32_t base = start; base < end; base += kThreads) {
         const bool all_done = __syncthreads_count(q.T < 0.0f) == kThreads;
         if (kStats && base != start) ph.lap(ph.walk);
@@ -688,9 +730,9 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
         a = b = c = make_float4(0.f, 0.f, 0.f, 0.f);
         if (idx < end) {
             const uint32_t g = g_next;
-            a = p.record[3 * (size_t)g];
-            b = p.record[3 * (size_t)g + 1];
-            c = p.record[3 * (size_t)g + 2];
+            a = vb.word01(g, 0);
+            b = vb.word01(g, 1);
+            c = vb.word2(g);
         }
         if (kStats && base == start) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -728,7 +770,7 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
         const int n = wave_compact(sM, cnt, 1u << wave, lane, sL[wave]);
         __syncthreads();  // list visible to the wave's other lanes
         if (kStats) ph.lap(ph.compact);
-        if (idx + kThreads < end) g_next = p.point_list[idx + kThreads];
+        if (idx + kThreads < end) g_next = vb.point_list[idx + kThreads];
         const uint32_t lb16 = 16u * (base - start + 1u);  // 16 x (list index of slot 0 + 1)
         uint32_t lo = 0xFFFFFFFFu;  // offset of the batch's last blended entry, per lane
         const int visited = walk_list(sL[wave], n, sA, sB, pxy, q.T, [&](float al, bool ok, uint32_t o) {
@@ -1555,11 +1597,12 @@ __global__ __launch_bounds__(kTilePixels) void k_render_backward(RenderParams p)
         const int kload = maxl - 1 - (done_cnt + t);
         uint32_t cover = 0;
         if (kload >= (int)lo) {
-            const uint32_t g = p.point_list[start + (uint32_t)kload];
+            const BoundView vb = bound_view(p);
+            const uint32_t g = vb.point_list[start + (uint32_t)kload];
             if (k5) s_gid[t] = g;
-            const float4 a = p.record[3 * (size_t)g];
-            const float4 b = p.record[3 * (size_t)g + 1];
-            const float4 c = p.record[3 * (size_t)g + 2];
+            const float4 a = vb.word01(g, 0);
+            const float4 b = vb.word01(g, 1);
+            const float4 c = vb.word2(g);
             const float cut = power_cutoff(b.y);
             sA[t] = make_float4(a.x, a.y, -0.5f * a.z, -0.5f * b.x);
             sB[t] = make_float4(a.w, b.y, cut, c.z);
@@ -1624,7 +1667,7 @@ __global__ __launch_bounds__(kTilePixels) void k_render_backward(RenderParams p)
             } else {
                 const int c = (kColor || cs < 6) ? cs : cs + 3;  // gslot's inverse
                 if (!gvalue<kColor, kGeo>(c)) continue;          // a value this variant does not produce
-                const uint32_t g = p.point_list[start + (uint32_t)(maxl - 1 - (done_cnt + e))];
+                const uint32_t g = bound_view(p).point_list[start + (uint32_t)(maxl - 1 - (done_cnt + e))];
                 atomicAdd(&p.grad[(size_t)g * kGradStride + c], v * flush_scale(c, p.W, p.H));
             }
         }

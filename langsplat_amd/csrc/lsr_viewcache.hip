@@ -71,6 +71,53 @@ __device__ __forceinline__ void move(T* set, T* pack, size_t i)
         pack[i] = set[i];
 }
 
+// radii item q: Gaussians 4 q .. 4 q + 3
+template <bool kRestore>
+__device__ __forceinline__ void move_radii(const ViewCopy& p, size_t q)
+{
+    if (p.radii_vec && 4 * q + 4 <= (size_t)p.P) {
+        move<kRestore>(reinterpret_cast<int4*>(p.radii), reinterpret_cast<int4*>(p.pk_radii), q);
+    } else {  // the caller's array ends at P and may sit at any 4-byte address
+        for (size_t j = 4 * q; j < 4 * q + 4 && j < (size_t)p.P; j++) move<kRestore>(p.radii, p.pk_radii, j);
+    }
+}
+
+// scheduled slot j: its class from the class counts (the pack's when restoring: the set's are written
+// by the same launch), then the list element
+template <bool kRestore>
+__device__ __forceinline__ void move_order(const ViewCopy& p, uint32_t j)
+{
+    const uint32_t* cnt = (kRestore ? p.pk_counters : p.counters) + kCntFwdClass;
+    uint32_t first = 0;
+    for (int c = 0; c < kWorkClasses; c++) {
+        const uint32_t n = min(cnt[c], (uint32_t)p.T);
+        if (j - first < n) {
+            uint32_t* slot = p.lists + (size_t)c * p.T + (j - first);
+            if (kRestore)
+                *slot = p.pk_order[j];
+            else
+                p.pk_order[j] = *slot;
+            break;
+        }
+        first += n;  // (j >= first still holds)
+    }
+}
+
+// counter word c of a set that receives a pack, as k_publish_counters leaves it: the five published
+// values, the forward's flags, the forward's class counts; every other word 0 (the overflow word, the
+// backward's class counts that the compositing adds to)
+__device__ __forceinline__ void restore_counter(const ViewCopy& p, int c)
+{
+    uint32_t v = 0u;
+    if (c == kCntRendered || c == kCntError || c == kCntSuper || c == kCntKeyMin || c == kCntKeyMax ||
+        (c >= kCntFwdClass && c < kCntBwdClass))
+        v = p.pk_counters[c];
+    else if (c == kCntFwdFlags)
+        v = p.fwd_flags;
+    p.counters[c] = v;
+    if (c == kCntOverflow && p.overflow) *p.overflow = 0;
+}
+
 template <bool kRestore>
 __global__ __launch_bounds__(kViewThreads) void k_view_copy(ViewCopy p)
 {
@@ -96,52 +143,54 @@ __global__ __launch_bounds__(kViewThreads) void k_view_copy(ViewCopy p)
             // (both arrays are padded past 4 ceil(R / 4) entries)
             move<kRestore>(p.point_list, p.pk_point_list, i - p.end[kSegRecord]);
         } else if (i < p.end[kSegRadii]) {
-            const size_t q = i - p.end[kSegPointList];
-            if (p.radii_vec && 4 * q + 4 <= (size_t)p.P) {
-                move<kRestore>(reinterpret_cast<int4*>(p.radii), reinterpret_cast<int4*>(p.pk_radii), q);
-            } else {  // the caller's array ends at P and may sit at any 4-byte address
-                for (size_t j = 4 * q; j < 4 * q + 4 && j < (size_t)p.P; j++) move<kRestore>(p.radii, p.pk_radii, j);
-            }
+            move_radii<kRestore>(p, i - p.end[kSegPointList]);
         } else if (i < p.end[kSegClamped]) {
             move<kRestore>(p.clamped, p.pk_clamped, i - p.end[kSegRadii]);
         } else if (i < p.end[kSegRanges]) {
             move<kRestore>(p.ranges, p.pk_ranges, i - p.end[kSegClamped]);
         } else if (i < p.end[kSegOrder]) {
-            // scheduled slot j: its class from the class counts (the pack's when restoring: the set's
-            // are written by this launch), then the list element
-            const uint32_t j = (uint32_t)(i - p.end[kSegRanges]);
-            const uint32_t* cnt = (kRestore ? p.pk_counters : p.counters) + kCntFwdClass;
-            uint32_t first = 0;
-            for (int c = 0; c < kWorkClasses; c++) {
-                const uint32_t n = min(cnt[c], (uint32_t)p.T);
-                if (j - first < n) {
-                    uint32_t* slot = p.lists + (size_t)c * p.T + (j - first);
-                    if (kRestore)
-                        *slot = p.pk_order[j];
-                    else
-                        p.pk_order[j] = *slot;
-                    break;
-                }
-                first += n;  // (j >= first still holds)
-            }
+            move_order<kRestore>(p, (uint32_t)(i - p.end[kSegRanges]));
         } else if (i < p.end[kSegCounters]) {
             const int c = (int)(i - p.end[kSegOrder]);
-            if (!kRestore) {
+            if (!kRestore)
                 p.pk_counters[c] = p.counters[c];
-            } else {
-                // as k_publish_counters leaves them: the five published values, the forward's flags, the
-                // forward's class counts; every other word 0 (the overflow word, the backward's class
-                // counts that the compositing adds to)
-                uint32_t v = 0u;
-                if (c == kCntRendered || c == kCntError || c == kCntSuper || c == kCntKeyMin || c == kCntKeyMax ||
-                    (c >= kCntFwdClass && c < kCntBwdClass))
-                    v = p.pk_counters[c];
-                else if (c == kCntFwdFlags)
-                    v = p.fwd_flags;
-                p.counters[c] = v;
-                if (c == kCntOverflow && p.overflow) *p.overflow = 0;
-            }
+            else
+                restore_counter(p, c);
         } else {  // restore: the fused loss's words start at 0 (the preprocess clears them)
+            p.loss_words[i - p.end[kSegCounters]] = make_uint4(0u, 0u, 0u, 0u);
+        }
+    }
+}
+
+// lsr_view_bind.  Segment kSegRecord is the plane's b word (one Gaussian per item), kSegPointList the
+// table (one item); the other segments are k_view_copy<true>'s.  identity (no pack): the table names
+// the set's own arrays and b comes from the set's records; only those two segments have items.
+__global__ __launch_bounds__(kViewThreads) void k_view_bind(ViewCopy p, float4* plane, ViewBind* bind, int identity)
+{
+    const size_t stride = (size_t)gridDim.x * kViewThreads;
+    for (size_t i = (size_t)blockIdx.x * kViewThreads + threadIdx.x; i < p.end[kSegs - 1]; i += stride) {
+        if (i < p.end[kSegRecord]) {  // .x only: the language slots .yzw belong to the feature fill
+            const float b = identity ? reinterpret_cast<const float*>(p.record + 3 * i + 2)[0] : p.pk_recb[i];
+            reinterpret_cast<float*>(plane + i)[0] = b;
+        } else if (i < p.end[kSegPointList]) {
+            ViewBind t;
+            t.rec01 = identity ? p.record : p.pk_rec01;
+            t.s01 = identity ? 3u : 2u;
+            t.recb = plane;
+            t.sb = 1u;
+            t.point_list = reinterpret_cast<const uint32_t*>(identity ? p.point_list : p.pk_point_list);
+            *bind = t;
+        } else if (i < p.end[kSegRadii]) {
+            move_radii<true>(p, i - p.end[kSegPointList]);
+        } else if (i < p.end[kSegClamped]) {
+            move<true>(p.clamped, p.pk_clamped, i - p.end[kSegRadii]);
+        } else if (i < p.end[kSegRanges]) {
+            move<true>(p.ranges, p.pk_ranges, i - p.end[kSegClamped]);
+        } else if (i < p.end[kSegOrder]) {
+            move_order<true>(p, (uint32_t)(i - p.end[kSegRanges]));
+        } else if (i < p.end[kSegCounters]) {
+            restore_counter(p, (int)(i - p.end[kSegOrder]));
+        } else {
             p.loss_words[i - p.end[kSegCounters]] = make_uint4(0u, 0u, 0u, 0u);
         }
     }
@@ -161,9 +210,8 @@ hipError_t launch_view_counts(const uint32_t* counters, uint32_t* host, hipStrea
     return hipGetLastError();
 }
 
-hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s)
+static ViewCopy view_copy_params(const ViewParams& v, const Layout& L)
 {
-    const Layout L = make_layout(v.P, v.W, v.H, v.R_cap, 0);  // point_list sits at offset 0
     const ViewPack V = make_view_pack(v.P, v.W, v.H, v.R);
     ViewCopy p{};
     p.P = v.P;
@@ -188,6 +236,19 @@ hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s)
     p.pk_ranges = reinterpret_cast<uint4*>(v.pack + V.ranges);
     p.pk_order = reinterpret_cast<uint32_t*>(v.pack + V.order);
     p.pk_point_list = reinterpret_cast<uint4*>(v.pack + V.point_list);
+    return p;
+}
+
+static dim3 view_grid(size_t n)
+{
+    const size_t blocks = (n + kViewThreads - 1) / kViewThreads;
+    return dim3((unsigned)(blocks < (size_t)kViewMaxBlocks ? blocks : (size_t)kViewMaxBlocks));
+}
+
+hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s)
+{
+    const Layout L = make_layout(v.P, v.W, v.H, v.R_cap, 0);  // point_list sits at offset 0
+    ViewCopy p = view_copy_params(v, L);
     const size_t P = (size_t)v.P, T = (size_t)L.tiles, R = (size_t)v.R;
     size_t n = 0;
     p.end[kSegRecord] = n += 3 * P;
@@ -198,12 +259,33 @@ hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s)
     p.end[kSegOrder] = n += T;
     p.end[kSegCounters] = n += restore ? (size_t)kCntWords : (size_t)kViewCounterWords;
     p.end[kSegLoss] = n += restore ? (T + 1) / 2 : 0;
-    const size_t blocks = (n + kViewThreads - 1) / kViewThreads;
-    const dim3 grid((unsigned)(blocks < (size_t)kViewMaxBlocks ? blocks : (size_t)kViewMaxBlocks));
+    const dim3 grid = view_grid(n);
     if (restore)
         hipLaunchKernelGGL(k_view_copy<true>, grid, dim3(kViewThreads), 0, s, p);
     else
         hipLaunchKernelGGL(k_view_copy<false>, grid, dim3(kViewThreads), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_view_bind(const ViewParams& v, bool clamped, hipStream_t s)
+{
+    const Layout L = make_layout(v.P, v.W, v.H, v.R_cap, 0);
+    const bool identity = v.pack == nullptr;
+    ViewParams vv = v;
+    if (identity) vv.R = 0;  // (no pack offset is used)
+    ViewCopy p = view_copy_params(vv, L);
+    const size_t P = (size_t)v.P, T = (size_t)L.tiles;
+    size_t n = 0;
+    p.end[kSegRecord] = n += P;
+    p.end[kSegPointList] = n += 1;
+    p.end[kSegRadii] = n += identity ? 0 : (P + 3) / 4;
+    p.end[kSegClamped] = n += identity || !clamped ? 0 : (P + 3) / 4;
+    p.end[kSegRanges] = n += identity ? 0 : (T + 1) / 2;
+    p.end[kSegOrder] = n += identity ? 0 : T;
+    p.end[kSegCounters] = n += identity ? 0 : (size_t)kCntWords;
+    p.end[kSegLoss] = n += identity ? 0 : (T + 1) / 2;
+    hipLaunchKernelGGL(k_view_bind, view_grid(n), dim3(kViewThreads), 0, s, p, reinterpret_cast<float4*>(v.geom + L.lang_plane),
+                       reinterpret_cast<ViewBind*>(v.geom + L.view_bind), identity ? 1 : 0);
     return hipGetLastError();
 }
 

@@ -128,7 +128,7 @@ class Adam(torch.optim.Optimizer):
         first (1 / N after a SUM all-reduce of N views' gradients; 1.0: as torch.optim.Adam).
         skip (inside a graph capture only): a device int32 flag; a replay that finds it set changes
         nothing (a view the rasterizer did not render, include/lsr.h lsr_adam_multi).
-        fill (inside a graph capture only): (record address, raw flags) -- the optimizer's one
+        fill (inside a graph capture only): (record address, raw flags[, plane]) -- the optimizer's one
         parameter is the language feature, and its updated value also goes into the language slots
         of that forward's render records (include/lsr.h lsr_adam_fill_language: the N > 1 language
         step, whose next composite then needs no fill)."""
@@ -185,7 +185,9 @@ class Adam(torch.optim.Optimizer):
                                    "P x 3 parameter (the language feature)")
             self._lr_order, self._lr_dev = order, None
             with _native._on_device(device):
-                _native._check(_native.load().lsr_adam_fill_language(
+                lib = _native.load()  # a third element set: the address is a bound set's plane
+                fn = lib.lsr_adam_fill_language_plane if len(fill) > 2 and fill[2] else lib.lsr_adam_fill_language
+                _native._check(fn(
                     ctypes.byref(entries[0]), float(grad_scale), ctypes.c_void_p(self._step_dev.data_ptr()),
                     None if skip is None else ctypes.c_void_p(skip.data_ptr()), ctypes.c_void_p(int(fill[0])),
                     int(fill[1]), _native._stream(device)), "lsr_adam_fill_language")

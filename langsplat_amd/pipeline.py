@@ -108,6 +108,20 @@ class ViewCache:
         native.save(r, num_rendered, pack)             set r's geometry into the pack (stream B)
         native.restore(r, num_rendered, pack)          the pack into set r (stream B)
 
+    and, for the bound form (include/lsr.h lsr_view_bind: the set reads the pack in place),
+
+        native.can_bind() -> bool                      the library has lsr_view_bind and the step's graphs
+                                                       were captured against the sets' tables
+        native.bind(r, num_rendered, pack)             set r bound to the pack (stream B)
+        native.step_done(r) -> bool                    set r's last enqueued step has finished
+
+    A hit then enqueues a bind in place of the restore; without can_bind (or when it says no) the
+    copying restore stays.  A bound set's composite and backward read the pack on stream A long
+    after the bind was enqueued, so the cache keeps a reference to the pack a set is bound to
+    (`bound`) whatever happens to `packs` -- invalidate() included -- until the set is next visited,
+    and from then (`retired`) until the set's step event has completed.  One pack may be bound into
+    several sets at once (binds only read it).
+
     A view's key is any hashable; `ref` is kept with it (the camera object: its id stays unique while
     the cache holds it).  There is no eviction: an epoch is a permutation of the views, so LRU would
     miss every time; once the budget is full the remaining views keep running their geometry graph."""
@@ -116,19 +130,33 @@ class ViewCache:
 
     def __init__(self, sets: int, budget_bytes: int, native):
         self.native = native
+        can = getattr(native, "can_bind", None)
+        self.bind = bool(can()) if can is not None else False
+        self.bound = [None] * sets      # per set: the pack its table names
+        self.retired = []               # (set, pack): no longer bound, its set's step may still read it
         self.budget = int(budget_bytes)
         self.packs = {}                 # key -> (ref, num_rendered, pack, nbytes)
         self.pending = [None] * sets    # per set: (key, ref, event, host counters) of a geometry graph's result
         self.stamp = None
+        self.off = False                # disable(): nothing is saved or hit any more
         self.bytes = self.hits = self.misses = self.drops = 0
 
     def invalidate(self):
-        """Drop every pack, and every set's claim to hold a result worth saving."""
+        """Drop every pack, and every set's claim to hold a result worth saving.  (A set bound to a
+        dropped pack keeps its reference, and goes on to composite the geometry it was given, as a
+        set that holds a restored copy does.)"""
         if self.packs:
             self.drops += 1
         self.packs.clear()
         self.pending = [None] * len(self.pending)
         self.bytes = 0
+
+    def disable(self):
+        """No view is cached from here on (a geometry tensor became trainable): every pack is dropped,
+        every visit is a miss and nothing is saved.  The cache object stays, because `bound` and
+        `retired` must: sets bound ahead still read their packs in steps not yet enqueued."""
+        self.invalidate()
+        self.off = True
 
     def check(self, stamp):
         """The geometry tensors' (data_ptr, _version) stamp at this replay: another one than the packs
@@ -141,7 +169,7 @@ class ViewCache:
     def computed(self, r, key, ref, event, host):
         """Set r's geometry graph was just enqueued for view `key`; `event` follows the copy of its
         counter slots into `host` (pinned).  Nothing is pending for a view that has a pack."""
-        self.pending[r] = None if key in self.packs else (key, ref, event, host)
+        self.pending[r] = None if self.off or key in self.packs else (key, ref, event, host)
 
     def visit(self, r, key) -> bool:
         """Set r is about to receive view `key` (its last reader is done, on stream B's order).  First
@@ -155,7 +183,7 @@ class ViewCache:
         """visit()'s first half: the view set r holds into a pack, under visit()'s conditions; True if
         it was saved.  Either way the set's claim is spent."""
         pend, self.pending[r] = self.pending[r], None
-        if pend is not None and pend[0] not in self.packs and pend[2].query():
+        if pend is not None and not self.off and pend[0] not in self.packs and pend[2].query():
             pkey, ref, _, host = pend
             if int(host[self.OVERFLOW]) == 0:
                 rendered = int(host[self.RENDERED])
@@ -174,10 +202,26 @@ class ViewCache:
         hit = self.packs.get(key)
         if hit is None:
             self.misses += 1
+            self._unbind(r)  # (the geometry graph gives the set its own arrays again)
             return False
-        self.native.restore(r, hit[1], hit[2])
+        if self.bind:
+            if self.bound[r] is not hit[2]:
+                self._unbind(r)
+            self.native.bind(r, hit[1], hit[2])
+            self.bound[r] = hit[2]
+        else:
+            self.native.restore(r, hit[1], hit[2])
         self.hits += 1
         return True
+
+    def _unbind(self, r):
+        """Set r is about to get other geometry: the pack it was bound to is kept until the set's last
+        enqueued step (its last reader) has finished; the retired ones whose step has are let go."""
+        if self.bound[r] is not None:
+            self.retired.append((r, self.bound[r]))
+            self.bound[r] = None
+        if self.retired:
+            self.retired = [(q, pack) for q, pack in self.retired if not self.native.step_done(q)]
 
     def stats(self):
         return {"hits": self.hits, "misses": self.misses, "packs": len(self.packs), "bytes": self.bytes,
@@ -190,8 +234,11 @@ class _ViewNative:
     stream, not the step: no reference cycle, so a step's graphs and packs are freed when its last
     reference goes (not by a later garbage collection, which could run inside a graph capture)."""
 
-    def __init__(self, sets, stream, device):
+    def __init__(self, sets, stream, device, bound=False, readers=(), ev_step=()):
         self.sets, self.stream, self.device = sets, stream, device
+        self.bound = bool(bound)   # the step's graphs read the sets' tables (lsr_view_bind)
+        self.readers = readers     # the streams whose kernels read a bound pack in place (stream A)
+        self.ev_step = ev_step     # the step's per-set events (the list: no reference to the step)
         self.args = {}  # (set, pack address and size, tile instances) -> LsrViewArgs
         call = sets[0].geometry_call
         self.dims = (call["P"], call["W"], call["H"])
@@ -201,7 +248,9 @@ class _ViewNative:
 
     def alloc(self, nbytes):
         pack = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
-        pack.record_stream(self.stream)  # used on stream B only, whatever stream allocates it
+        pack.record_stream(self.stream)  # used on stream B, whatever stream allocates it
+        for s in self.readers:           # ... and, bound, read in place by the steps on stream A
+            pack.record_stream(s)
         return pack
 
     def _args(self, r, rendered, pack):
@@ -216,6 +265,16 @@ class _ViewNative:
 
     def restore(self, r, rendered, pack):
         _native.view_restore(self._args(r, rendered, pack), self.stream)
+
+    def can_bind(self):
+        return self.bound and _native.has_view_bind()
+
+    def bind(self, r, rendered, pack):
+        # (the language step reads no clamped bits: lsr_view_bind's LSR_BIND_CLAMPED stays off)
+        _native.view_bind(self._args(r, rendered, pack), self.stream)
+
+    def step_done(self, r):
+        return self.ev_step[r].query()
 
 
 class PipelinedGraphStep:
@@ -294,6 +353,14 @@ class PipelinedGraphStep:
     it after changing a camera object's tensors in place.  Rotation mode keeps its geometry graphs (no
     cache).  view_cache_stats() counts hits, misses, packs and bytes.
 
+    Bound form (the default when the library has lsr_view_bind): the composite, the backward and the
+    update's feature fill are captured against each set's table and plane (include/lsr.h "the bound
+    form"), a miss's geometry graph writes the identity table itself, and a hit enqueues
+    lsr_view_bind -- about 30 MB of traffic at C3 -- in place of the 157 MB restore: the set reads
+    the pack's records and point list where they are.  Every form of the step is bound (the fused
+    tail, the N > 1 deferred tail, the N > 1 update with lsr_adam_fill_language, the plain composite
+    fill); view_cache="copy" forces the copying restore (A/B runs, tests).
+
     Knobs: the `sets` argument (default 3), LSR_PG_ROT (the `rotation` argument's default),
     LSR_PG_DEFER=0 (N > 1: the gradient epilogue stays in the backward) and LSR_PG_NATIVE_LAUNCH=0
     (every replay through torch's stream context).  Forms measured at C3 and not kept (DESIGN.md
@@ -345,6 +412,8 @@ class PipelinedGraphStep:
         self._loaded = [None] * S  # the view each set's slot holds (slots only)
         self._assigned = [None] * S  # rotation mode: the view each set's next geometry renders
         self.view_cache = bool(view_cache)
+        self.view_copy = view_cache == "copy"  # the copying restore even where the sets could be bound
+        self.bound = False  # the graphs were captured against the sets' tables and planes (set by capture)
         self.view_cache_bytes = view_cache_bytes
         self._views = None  # the ViewCache while it is active (set by capture)
 
@@ -386,7 +455,10 @@ class PipelinedGraphStep:
         """views: the first S - 1 views (camera, gt, mask) when the step renders from ViewSlots (a
         shorter list repeats its last view); the capacities are measured on them."""
         S = self.S
-        self._views = None  # every pack goes before anything is measured or captured
+        # every pack goes before anything is measured or captured.  (Safe for bound sets: every step
+        # enqueued so far precedes this drop -- the packs are recorded on both streams -- and no later
+        # step reads them: after a capture every set gets its geometry again, primed = False.)
+        self._views = None
         if self.slots is not None:
             if not views:
                 raise ValueError("PipelinedGraphStep.capture: the first views are needed with slots")
@@ -403,6 +475,12 @@ class PipelinedGraphStep:
         # their streams: released, so the warm-up and the captures create their own (graph.py)
         self.key = capture_key(self.model, self.optimizer, self.params)
         self.stale_released = release_stale_accumulators(self.params)
+        # the bound form wherever the view cache can become active (decided before any set is touched:
+        # every capture below and every fill target follows it)
+        self.bound = (self.view_cache and not self.view_copy and self.model is not None and self.R == 1
+                      and self._geometry_tensors() is not None and _native.has_view_bind())
+        for st in self.sets:
+            st.view_bind = self.bound
         self._measure(min_rendered, min_entries)
         self._reset_graphs()
         self.optimizer.prepare_capture()
@@ -461,13 +539,15 @@ class PipelinedGraphStep:
         def update_ctx(p):
             if defer:  # this set's deferred tail (its arguments stay with the context)
                 self._tails[p] = _native.fused_update(self.optimizer, self.params[0], skip=self.overflow[p],
-                                                      fill=self._record_ptr((p + 1) % S), defer=True)
+                                                      fill=self._record_ptr((p + 1) % S), defer=True,
+                                                      fill_plane=self.bound)
                 return self._tails[p]
             return _native.fused_update(self.optimizer, self.params[0], skip=self.overflow[p],
-                                        fill=self._record_ptr((p + 1) % S)) if fused else _nullctx()
+                                        fill=self._record_ptr((p + 1) % S),
+                                        fill_plane=self.bound) if fused else _nullctx()
 
-        def adam_fill(p):  # (N > 1) the set's update fills the next set's records
-            return (self._record_ptr((p + 1) % S), _native.RAW_LANGUAGE) if fill_after else None
+        def adam_fill(p):  # (N > 1) the set's update fills the next set's records (bound: its plane)
+            return (self._record_ptr((p + 1) % S), _native.RAW_LANGUAGE, self.bound) if fill_after else None
 
         def step_body(p, loss):
             with update_ctx(p):  # the backward runs on its forward's stream (sa)
@@ -558,7 +638,9 @@ class PipelinedGraphStep:
         self._cnt_size = (call["W"], call["H"])
         self._cnt_dev = [st.tensors[("scratch", _native.LSR_BUF_IMAGE)] for st in self.sets]
         self._cnt_host = [torch.zeros((8,), dtype=torch.int32).pin_memory() for _ in self.sets]
-        return ViewCache(self.S, budget, _ViewNative(self.sets, self.streams[1], self.params[0].device))
+        return ViewCache(self.S, budget, _ViewNative(self.sets, self.streams[1], self.params[0].device,
+                                                     bound=self.bound, readers=(self.streams[0],) if self.bound else (),
+                                                     ev_step=self.ev_step))
 
     def _view_key(self, r):
         """(key, reference) of the view set r's geometry renders: its camera object, or the fixed view."""
@@ -684,10 +766,13 @@ class PipelinedGraphStep:
             self.bucket.all_reduce(average=True, flag=self.overflow[p])
 
     def _record_ptr(self, p):
-        """Device address of set p's per-Gaussian render records (include/lsr.h lsr_state_layout.record)."""
+        """Device address of where set p's language slots live: its per-Gaussian render records (include/lsr.h
+        lsr_state_layout.record), or -- bound -- its plane (lsr_view_bind_layout)."""
         geom = self.sets[p].tensors[("scratch", _native.LSR_BUF_GEOM)]
         _, H, W = self.sets[p].tensors[("out", "color")].shape
         P = int(self.params[0].shape[0])
+        if self.bound:
+            return geom.data_ptr() + _native.view_bind_layout(P, int(W), int(H))["plane"]
         return geom.data_ptr() + _native.state_layout(P, int(W), int(H), 0)["record"]
 
     def _geometry(self, r, released=None):
@@ -712,8 +797,9 @@ class PipelinedGraphStep:
                 # released: a one-wave kernel before the set's own event.  (Stream B is a first epoch's
                 # critical path: a device-to-host copy with an event of its own there measured +0.05 ms
                 # per step, the same copy on a third stream +0.07, profiles/view_cache_ab.txt.)
-                _native.view_counts(*self._cnt_size, self._cnt_dev[r], self._cnt_host[r], sb)
-                vc.computed(r, key, ref, self.ev_geo[r], self._cnt_host[r])
+                if not vc.off:
+                    _native.view_counts(*self._cnt_size, self._cnt_dev[r], self._cnt_host[r], sb)
+                    vc.computed(r, key, ref, self.ev_geo[r], self._cnt_host[r])
         self.ev_geo[r].record(sb)
 
     def _launcher(self, p, fast):
@@ -755,8 +841,11 @@ class PipelinedGraphStep:
             return self._replay_rotation(next_view, wait)
         if self._views is not None:
             ts = self._geometry_tensors()
-            if ts is None:  # a geometry tensor became trainable: no cache until the next capture
-                self._views = None
+            if ts is None:
+                # a geometry tensor became trainable: no cache until the next capture.  The cache is
+                # switched off, not discarded: it holds the packs that sets bound ahead still read
+                if not self._views.off:
+                    self._views.disable()
             else:
                 self._views.check(tuple((t.data_ptr(), t._version) for t in ts))
         S = self.S
@@ -873,7 +962,7 @@ class PipelinedGraphStep:
         """Set p's records' language slots from the parameter as it is now (on the current stream),
         for a composite that would otherwise blend what the previous step's fused tail wrote."""
         radii = self.sets[p].tensors[("out", "radii")]
-        _native.fill_language(self.params[0], _native.RAW_LANGUAGE, radii, self._record_ptr(p))
+        _native.fill_language(self.params[0], _native.RAW_LANGUAGE, radii, self._record_ptr(p), plane=self.bound)
 
     def synchronize(self):
         """The caller's current stream waits for every replay enqueued so far (both streams)."""

@@ -80,6 +80,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _f32(rotations), _f32(cov3Ds_precomp))
         flags = _forward_flags(ctx, grad_enabled)
         ctx.records_zeroed = flags == _native.FWD_ZERO_GRAD_RECORDS
+        ctx.view_bound = _native.forward_bound()  # the backward reads the set's table as the forward does
         if raster_settings.debug:
             cpu_args = _cpu_deep_copy(args)
             try:
@@ -110,7 +111,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         args = (means3D, sh, colors_precomp, lang if ctx.use_lang else None, scales, rotations, cov3Ds_precomp,
                 radii, grad_out_color, gl, ctx.num_rendered, geom, binning, image)
         geometry = _native.geometry_grads_needed(ctx.needs_input_grad, (0, 2, 3, 5, 6, 7, 8))
-        flags = _native.BWD_RECORDS_ZEROED if ctx.records_zeroed else 0
+        flags = (_native.BWD_RECORDS_ZEROED if ctx.records_zeroed else 0) | (
+            _native.BIND_BACKWARD if ctx.view_bound else 0)
         ctx.records_zeroed = False  # a second backward (retain_graph) clears its own records
         if rs.debug:
             cpu_args = _cpu_deep_copy(args)
@@ -203,6 +205,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
         # the language step (train.py:96-104): the loss is the fused language loss, so the colour
         # image is expected off the loss path and the split-replay states skip the colour sums; a
         # colour gradient arriving anyway is served by rasterizing again with them (backward below)
+        ctx.view_bound = _native.forward_bound()  # the backward reads the set's table as the forward does
         ctx.no_color = fuse_loss and ctx.records_zeroed
         if ctx.no_color:
             flags |= _native.FWD_NO_COLOR_GRAD
@@ -259,7 +262,7 @@ class _RasterizeGaussiansFused(torch.autograd.Function):
         gl = grad_out_language_feature if ctx.use_lang else None
         geometry = _native.geometry_grads_needed(ctx.needs_input_grad, (0, 2, 3, 4, 5, 6))
         flags = (_native.BWD_RECORDS_ZEROED if ctx.records_zeroed else 0) | (
-            _native.BWD_SHARED_CU if ctx.shared_cu else 0)
+            _native.BWD_SHARED_CU if ctx.shared_cu else 0) | (_native.BIND_BACKWARD if ctx.view_bound else 0)
         ctx.records_zeroed = False  # a second backward (retain_graph) clears its own records
         # a captured N = 1 language step may fuse its Adam step into this backward's epilogue
         fu = _native.fused_update.active()
