@@ -538,6 +538,57 @@ typedef struct lsr_query_args {
 } lsr_query_args;
 int32_t lsr_query_relevancy(const lsr_query_args* args, void* stream);
 
+/* lsr_query_semantic: OpenCLIPNetwork.get_semantic_map (eval/openclip_encoder.py:82-94) on the same
+ * decoded pixels, in ONE kernel: an open-vocabulary segmentation.  The decoder, the normalisation and
+ * the cosine similarities s_k with the n_labels + n_neg phrases (labels first) are lsr_query_relevancy's,
+ * bit for bit.  Per pixel:
+ *     out_label = argmax_k softmax(10 s)_k, and -1 where a negative wins (k >= n_labels).  Softmax is
+ *                 monotone, so this is the FIRST index of the largest s_k (torch.argmax's tie rule: a
+ *                 scan from k = 0 with a strict >; a label beats a negative of equal similarity);
+ *     out_score = the winner's softmax value, 1 / sum_k exp(10 (s_k - s_max)), summed in index order
+ *                 (for a -1 pixel: the winning negative's probability).  NULL: not computed.
+ * A pixel whose decoded norm is 0 has every s_k NaN: label 0 (as torch.argmax gives) and a NaN score.
+ * Limits, refusals (LSR_ERR_INVALID before any device work; out_label must be non-NULL), N == 0 and
+ * the call's behaviour (one kernel, no wait, no atomics, bit-identical between calls) are
+ * lsr_query_relevancy's.
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+typedef struct lsr_query_semantic_args {
+    int64_t N;                    /* pixels */
+    const float* feature;         /* as lsr_query_args */
+    int64_t channel_stride, pixel_stride;
+    int32_t n_layers;
+    const int32_t* widths;        /* HOST int32[n_layers] */
+    const float* weights;         /* device, as lsr_query_args */
+    int32_t n_labels, n_neg;
+    const float* phrases;         /* device: (n_labels + n_neg) x D, labels first */
+    int32_t* out_label;           /* device: N labels, 0 .. n_labels - 1 or -1 */
+    float* out_score;             /* NULL, or device: N floats */
+} lsr_query_semantic_args;
+int32_t lsr_query_semantic(const lsr_query_semantic_args* args, void* stream);
+
+/* lsr_label_stats: what one does with label maps -- per-class counts of n_maps predicted maps against
+ * ground truth, N pixels each.  gt has gt_maps = 1 map (shared by every predicted map) or n_maps.
+ * A pixel is valid exactly when 0 <= gt < n_classes (any other value is an ignore label: the pixel
+ * counts nowhere).  A valid pixel of class g adds one to ground_truth[g] and to valid; if
+ * 0 <= pred < n_classes, one to predicted[pred]; if pred == g, one to intersection[g] and to correct.
+ * A prediction of -1 (or any value outside the classes) on a valid pixel is a miss and counts in no
+ * predicted cell.  The union of a class is predicted + ground_truth - intersection.
+ * The call clears its outputs on the stream itself, enqueues one kernel (per 65535 maps) and does not
+ * wait.  Integer atomics only: the counts are exact and identical between calls.  LSR_ERR_INVALID
+ * before any device work for null args or pointers, n_classes outside 1..64, gt_maps neither 1 nor
+ * n_maps, N < 0 or above 2^40, n_maps < 0, outputs not 8-byte aligned.  n_maps == 0 or N == 0 is valid
+ * and enqueues nothing (the outputs are not touched).
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+typedef struct lsr_label_stats_args {
+    int64_t N;                    /* pixels per map */
+    int32_t n_maps, gt_maps, n_classes;
+    const int32_t* pred;          /* device: n_maps x N */
+    const int32_t* gt;            /* device: gt_maps x N */
+    int64_t* out_counts;          /* device: n_maps x n_classes x 3 (intersection, predicted, ground truth) */
+    int64_t* out_totals;          /* device: n_maps x 2 (correct, valid) */
+} lsr_label_stats_args;
+int32_t lsr_label_stats(const lsr_label_stats_args* args, void* stream);
+
 /* ---- LERF evaluation -----------------------------------------------------
  * What activate_stream and lerf_localization (eval/evaluate_iou_loc.py:90-217) do with
  * get_max_across's (levels, n_prompts, H, W) relevancy after their first line, for n_maps = levels *

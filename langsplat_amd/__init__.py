@@ -9,6 +9,7 @@ from .loss import rgb_loss, ssim  # noqa: F401
 from .levels import LevelsStep, render_levels, render_levels_train, split_levels, stack_levels  # noqa: F401
 from .levels_graph import GraphedLevelsStep, LevelsViewSlot  # noqa: F401
 from .query import Decoder, decode, relevancy_map, render_levels_relevancy, render_relevancy  # noqa: F401
+from .query import label_stats, render_levels_semantic, render_semantic, semantic_map  # noqa: F401
 from .rasterizer import GaussianRasterizationSettings, GaussianRasterizer, rasterize_gaussians  # noqa: F401
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "rasterize_gaussians",

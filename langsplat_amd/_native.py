@@ -120,6 +120,18 @@ class LsrQueryArgs(ctypes.Structure):
                 ("n_neg", ctypes.c_int32), ("phrases", _vp), ("out_relevancy", _vp), ("out_decoded", _vp)]
 
 
+class LsrQuerySemanticArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int64), ("feature", _vp), ("channel_stride", ctypes.c_int64),
+                ("pixel_stride", ctypes.c_int64), ("n_layers", ctypes.c_int32),
+                ("widths", ctypes.POINTER(ctypes.c_int32)), ("weights", _vp), ("n_labels", ctypes.c_int32),
+                ("n_neg", ctypes.c_int32), ("phrases", _vp), ("out_label", _vp), ("out_score", _vp)]
+
+
+class LsrLabelStatsArgs(ctypes.Structure):
+    _fields_ = [("N", ctypes.c_int64), ("n_maps", ctypes.c_int32), ("gt_maps", ctypes.c_int32),
+                ("n_classes", ctypes.c_int32), ("pred", _vp), ("gt", _vp), ("out_counts", _vp), ("out_totals", _vp)]
+
+
 class LsrEvalStats(ctypes.Structure):
     _fields_ = [("blend_min", ctypes.c_float), ("blend_max", ctypes.c_float), ("avg_max", ctypes.c_float),
                 ("avg_argmax", ctypes.c_int32)]
@@ -187,6 +199,8 @@ SIGNATURES = {
                                                   ctypes.POINTER(LsrLevelsStepBackwardArgs), _vp]),
     "lsr_mark_visible": (ctypes.c_int32, [ctypes.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "lsr_query_relevancy": (ctypes.c_int32, [ctypes.POINTER(LsrQueryArgs), _vp]),
+    "lsr_query_semantic": (ctypes.c_int32, [ctypes.POINTER(LsrQuerySemanticArgs), _vp]),
+    "lsr_label_stats": (ctypes.c_int32, [ctypes.POINTER(LsrLabelStatsArgs), _vp]),
     "lsr_eval_filter": (ctypes.c_int32, [ctypes.POINTER(LsrEvalFilterArgs), _vp]),
     "lsr_eval_masks": (ctypes.c_int32, [ctypes.POINTER(LsrEvalMaskArgs), _vp]),
     "lsr_rgb_loss_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),

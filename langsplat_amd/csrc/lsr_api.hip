@@ -1400,6 +1400,60 @@ int32_t lsr_query_relevancy(const lsr_query_args* a, void* stream_ptr)
     return LSR_OK;
 }
 
+int32_t lsr_query_semantic(const lsr_query_semantic_args* a, void* stream_ptr)
+{
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_query_semantic: null args");
+    if (a->N < 0 || a->N > (int64_t)INT32_MAX * kQPix) return fail(LSR_ERR_INVALID, "lsr_query_semantic: invalid N");
+    if (a->n_layers < 1 || a->n_layers > kQueryMaxLayers)
+        return fail(LSR_ERR_INVALID, "lsr_query_semantic: invalid n_layers (1 to 8 layers)");
+    if (!a->widths) return fail(LSR_ERR_INVALID, "lsr_query_semantic: null widths");
+    QueryParams p{};
+    int off = 0;
+    for (int l = 0; l < a->n_layers; l++) {
+        const int wd = a->widths[l];
+        if (wd < 16 || wd > 512 || wd % 16 != 0)
+            return fail(LSR_ERR_INVALID, "lsr_query_semantic: invalid width (a multiple of 16, at most 512)");
+        p.widths[l] = wd;
+        p.w_off[l] = off;
+        off += wd * (l ? a->widths[l - 1] : 3) + wd;
+    }
+    if (a->n_labels < 1 || a->n_neg < 1 || a->n_labels + a->n_neg > 64)
+        return fail(LSR_ERR_INVALID, "lsr_query_semantic: invalid phrase counts (n_labels >= 1, n_neg >= 1, at most 64)");
+    if (!a->feature || !a->weights || !a->phrases || !a->out_label)
+        return fail(LSR_ERR_INVALID, "lsr_query_semantic: null pointer");
+    if (((reinterpret_cast<uintptr_t>(a->weights) | reinterpret_cast<uintptr_t>(a->phrases)) & 15) != 0)
+        return fail(LSR_ERR_INVALID, "lsr_query_semantic: weights and phrases must be 16-byte aligned");
+    p.N = a->N;
+    p.feature = a->feature;
+    p.channel_stride = a->channel_stride;
+    p.pixel_stride = a->pixel_stride;
+    p.n_layers = a->n_layers;
+    p.weights = a->weights;
+    p.n_pos = a->n_labels;
+    p.n_neg = a->n_neg;
+    p.phrases = a->phrases;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    LSR_TRY(launch_query(p, stream, a->out_label, a->out_score), "query semantic");
+    return LSR_OK;
+}
+
+int32_t lsr_label_stats(const lsr_label_stats_args* a, void* stream_ptr)
+{
+    if (!a) return fail(LSR_ERR_INVALID, "lsr_label_stats: null args");
+    if (a->N < 0 || a->N > kLabelStatsMaxN || a->n_maps < 0) return fail(LSR_ERR_INVALID, "lsr_label_stats: invalid size");
+    if (a->n_classes < 1 || a->n_classes > 64) return fail(LSR_ERR_INVALID, "lsr_label_stats: invalid n_classes (1 to 64)");
+    if (a->gt_maps != 1 && a->gt_maps != a->n_maps)
+        return fail(LSR_ERR_INVALID, "lsr_label_stats: invalid gt_maps (1, or n_maps)");
+    if (!a->pred || !a->gt || !a->out_counts || !a->out_totals) return fail(LSR_ERR_INVALID, "lsr_label_stats: null pointer");
+    if (((reinterpret_cast<uintptr_t>(a->out_counts) | reinterpret_cast<uintptr_t>(a->out_totals)) & 7) != 0)
+        return fail(LSR_ERR_INVALID, "lsr_label_stats: out_counts and out_totals must be 8-byte aligned");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    LSR_TRY(launch_label_stats(*a, stream), "label stats");
+    return LSR_OK;
+}
+
 // the checks lsr_eval_filter and lsr_eval_masks share; null when the shape is valid
 static const char* eval_shape_error(int32_t n_maps, int32_t H, int32_t W)
 {

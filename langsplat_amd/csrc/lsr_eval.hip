@@ -18,6 +18,8 @@
 //   k_eval_masks: the raw mask of the tile plus a 3-pixel halo (38 x 70) is recomputed from blend
 //     into LDS (zero outside the image), then 7 taps along x and 7 along y count the window's ones;
 //     smooth()'s exclusive upper bound clipped to H - 1 / W - 1 is a predicate on the tap's row / column.
+//   k_label_stats (lsr_label_stats): per-class counts of predicted against ground-truth labels, LDS
+//     counters per workgroup and one integer atomic per non-zero counter (see the kernel).
 // Statistics and counts: wave shuffles, 4 partials through LDS, then one integer atomic per
 // workgroup and value (min / max of order-preserving keys, add of counts): the result does not
 // depend on the order, so two runs are bit-identical.
@@ -332,6 +334,62 @@ __global__ __launch_bounds__(kEThreads) void k_eval_masks(const lsr_eval_mask_ar
     }
 }
 
+// lsr_label_stats: per-class counts of a predicted against a ground-truth label map.  A workgroup
+// takes kLSweep = 2048 consecutive pixels of one map per sweep (grid-stride over the map: more than
+// one sweep only past kLMaxBlocks * kLSweep pixels).  Every load of a sweep is issued before the first
+// LDS update waits for one (addresses clamped into the map, the value past it discarded).  Counters
+// live in LDS as 32-bit integers (a workgroup sees fewer than 2^32 pixels: launch_label_stats' bound on
+// N); only the non-zero ones are flushed, one 64-bit integer atomic each.  Integer adds commute, so the
+// result is exact and two calls are identical.
+constexpr int kLItems = 8;
+constexpr int kLSweep = kEThreads * kLItems;  // 2048
+constexpr int kLMaxBlocks = 1024;
+constexpr int kLMaxClasses = 64;
+
+__global__ __launch_bounds__(kEThreads) void k_label_stats(const lsr_label_stats_args p, int map0)
+{
+    __shared__ unsigned int cnt[kLMaxClasses * 3];  // per class: intersection, predicted, ground truth
+    __shared__ unsigned int tot[2];                 // correct, valid
+    const int tid = threadIdx.x;
+    const int m = map0 + (int)blockIdx.y;
+    const int C = p.n_classes;
+    const int32_t* pred = p.pred + (size_t)m * (size_t)p.N;
+    const int32_t* gt = p.gt + (p.gt_maps == 1 ? (size_t)0 : (size_t)m * (size_t)p.N);
+    for (int i = tid; i < 3 * C; i += kEThreads) cnt[i] = 0u;
+    if (tid < 2) tot[tid] = 0u;
+    __syncthreads();
+    for (int64_t base = (int64_t)blockIdx.x * kLSweep; base < p.N; base += (int64_t)gridDim.x * kLSweep) {
+        int pv[kLItems], gv[kLItems];
+#pragma unroll
+        for (int k = 0; k < kLItems; k++) {
+            const int64_t i = base + k * kEThreads + tid;
+            const int64_t ic = i < p.N ? i : p.N - 1;
+            pv[k] = pred[ic];
+            gv[k] = gt[ic];
+        }
+#pragma unroll
+        for (int k = 0; k < kLItems; k++) {
+            const int g = gv[k], q = pv[k];
+            if (base + k * kEThreads + tid < p.N && (unsigned)g < (unsigned)C) {
+                atomicAdd(&cnt[3 * g + 2], 1u);
+                if ((unsigned)q < (unsigned)C) atomicAdd(&cnt[3 * q + 1], 1u);
+                if (q == g) atomicAdd(&cnt[3 * g], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    // correct = sum of the intersections, valid = sum of the ground-truth counts
+    if (tid < C) {
+        if (cnt[3 * tid]) atomicAdd(&tot[0], cnt[3 * tid]);
+        if (cnt[3 * tid + 2]) atomicAdd(&tot[1], cnt[3 * tid + 2]);
+    }
+    unsigned long long* oc = reinterpret_cast<unsigned long long*>(p.out_counts) + (size_t)m * 3 * (size_t)C;
+    for (int i = tid; i < 3 * C; i += kEThreads)
+        if (cnt[i]) atomicAdd(oc + i, (unsigned long long)cnt[i]);
+    __syncthreads();
+    if (tid < 2 && tot[tid]) atomicAdd(reinterpret_cast<unsigned long long*>(p.out_totals) + 2 * (size_t)m + tid, (unsigned long long)tot[tid]);
+}
+
 unsigned eval_tiles(int H, int W)
 {
     return (unsigned)(((H + kETh - 1) / kETh) * ((W + kETw - 1) / kETw));  // H W < 2^31: fewer than 2^20 tiles
@@ -363,6 +421,22 @@ hipError_t launch_eval_masks(const lsr_eval_mask_args& a, hipStream_t s)
     for (int map0 = 0; map0 < a.n_maps; map0 += kEMaxGridY) {
         const int n = a.n_maps - map0 < kEMaxGridY ? a.n_maps - map0 : kEMaxGridY;
         hipLaunchKernelGGL(k_eval_masks, dim3(eval_tiles(a.H, a.W), (unsigned)n), dim3(kEThreads), 0, s, a, map0);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_label_stats(const lsr_label_stats_args& a, hipStream_t s)
+{
+    if (a.n_maps == 0 || a.N == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(a.out_counts, 0, 3 * sizeof(int64_t) * (size_t)a.n_maps * (size_t)a.n_classes, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(a.out_totals, 0, 2 * sizeof(int64_t) * (size_t)a.n_maps, s);
+    if (e != hipSuccess) return e;
+    const int64_t sweeps = (a.N + kLSweep - 1) / kLSweep;
+    const unsigned blocks = (unsigned)(sweeps < kLMaxBlocks ? sweeps : kLMaxBlocks);
+    for (int map0 = 0; map0 < a.n_maps; map0 += kEMaxGridY) {
+        const int n = a.n_maps - map0 < kEMaxGridY ? a.n_maps - map0 : kEMaxGridY;
+        hipLaunchKernelGGL(k_label_stats, dim3(blocks, (unsigned)n), dim3(kEThreads), 0, s, a, map0);
     }
     return hipGetLastError();
 }

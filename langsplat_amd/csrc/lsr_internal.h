@@ -516,11 +516,17 @@ struct QueryParams {
     // chunk (16 / 8 / 4, the most that fits), column stride of a staged weight row
     int act_floats, kc, ws;
 };
-hipError_t launch_query(QueryParams& p, hipStream_t s);
+// out_label non-null: lsr_query_semantic's kernel (n_pos = its number of labels; out_relevancy and
+// out_decoded are not read), with out_score NULL or N floats
+hipError_t launch_query(QueryParams& p, hipStream_t s, int32_t* out_label = nullptr, float* out_score = nullptr);
 
 // lsr_eval_filter / lsr_eval_masks (lsr_eval.hip): the validated public argument structs as they are
 hipError_t launch_eval_filter(const lsr_eval_filter_args& a, hipStream_t s);
 hipError_t launch_eval_masks(const lsr_eval_mask_args& a, hipStream_t s);
+// lsr_label_stats (lsr_eval.hip): clears the outputs on the stream, then counts; a workgroup's LDS
+// counters are 32-bit, which N <= kLabelStatsMaxN keeps from overflowing (1024 workgroups per map)
+constexpr int64_t kLabelStatsMaxN = (int64_t)1 << 40;
+hipError_t launch_label_stats(const lsr_label_stats_args& a, hipStream_t s);
 
 // lsr_view_save / lsr_view_restore (lsr_viewcache.hip): byte offsets of a view pack's segments, each
 // 16-byte aligned (include/lsr.h lsr_view_pack_bytes documents the sizes)

@@ -25,6 +25,8 @@
 //     then r[j, px] = 1 / (1 + exp(10 (max_n s_n - s_j))): the minimum over the negatives of a
 //     function that decreases in s_n is its value at the largest s_n.
 // No atomics; every sum has a fixed order, so two runs are bit-identical.
+// k_query_semantic (lsr_query_semantic) is the same body with another epilogue: a label and its
+// softmax value per pixel instead of the relevancies (see the kernel).
 #include <mutex>
 
 #include "lsr_internal.h"
@@ -377,6 +379,148 @@ __global__ __launch_bounds__(kQThreads) void k_query(const QueryParams p)
     }
 }
 
+// lsr_query_semantic: OpenCLIPNetwork.get_semantic_map (eval/openclip_encoder.py:82-94) on the same
+// on-chip similarities.  Everything up to and including the sims table is k_query's body without
+// out_decoded, over the same __device__ functions; it is a kernel of its own because k_query sits at
+// 256 VGPRs with spills and any restructuring of its text (a template over the epilogue, a shared
+// body function) changes its code.  Only the epilogue after the second barrier differs:
+//     label[px] = first index of the largest s_k (a scan from k = 0 with a strict >: torch.argmax's tie
+//                 rule; softmax is monotone, so this is argmax_k softmax(10 s)_k), -1 from n_pos on;
+//     score[px] = 1 / sum_k exp(10 (s_k - s_max)), summed in index order: the winner's softmax value.
+// All-NaN similarities (a decoded norm of 0) keep index 0 and give a NaN score, as torch.argmax does.
+__global__ __launch_bounds__(kQThreads) void k_query_semantic(const QueryParams p, int32_t* out_label, float* out_score)
+{
+    extern __shared__ float s_q[];
+    float* act = s_q;
+    float* wl = s_q + p.act_floats;
+    const int tid = threadIdx.x, lane = tid & 63, j = lane & 31, h = lane >> 5;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t px0 = (int64_t)blockIdx.x * kQPix;
+
+    {
+        const int f = tid >> 6, px = tid & 63;
+        float x = 0.f;
+        if (f < 3 && px0 + px < p.N) x = p.feature[(int64_t)f * p.channel_stride + (px0 + px) * p.pixel_stride];
+        if (f < 4) act[f * 64 + (px ^ ((f & 1) << 5))] = x;
+    }
+
+    f32x16 acc[kQTiles][2];
+    for (int l = 0; l + 1 < p.n_layers; l++) {
+        const LayerDims d = layer_dims(p, l);
+        layer_gemm(p, d, l, w, act, wl, acc);
+#pragma unroll
+        for (int q = 0; q < kQTiles; q++) {
+            const int t = w + kQWaves * q;
+            if (t < d.tiles) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int f = t * 32 + acc_row(r, h);
+                    if (f < d.n_out) {
+                        float* row = act + f * 64;
+                        const int sw = (f & 1) << 5;
+                        row[j ^ sw] = fmaxf(acc[q][0][r], 0.f);
+                        row[(32 + j) ^ sw] = fmaxf(acc[q][1][r], 0.f);
+                    }
+                }
+            }
+        }
+    }
+
+    const LayerDims d = layer_dims(p, p.n_layers - 1);
+    const int D = d.n_out, K = p.n_pos + p.n_neg;
+    layer_gemm(p, d, p.n_layers - 1, w, act, wl, acc);
+    f32x16 dots[2][2];
+    float nrm[2] = {0.f, 0.f};
+#pragma unroll
+    for (int pt = 0; pt < 2; pt++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) dots[pt][0][r] = dots[pt][1][r] = 0.f;
+    const float* prow0 = p.phrases + (size_t)(j < K ? j : K - 1) * D;
+    const float* prow1 = p.phrases + (size_t)(32 + j < K ? 32 + j : K - 1) * D;
+#pragma unroll
+    for (int q = 0; q < kQTiles; q++) {
+        const int t = w + kQWaves * q;
+        if (t < d.tiles) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                nrm[0] = fmaf(acc[q][0][r], acc[q][0][r], nrm[0]);
+                nrm[1] = fmaf(acc[q][1][r], acc[q][1][r], nrm[1]);
+            }
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const int f = t * 32 + 8 * g + 4 * h;
+                float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+                if (f < D) {
+                    a0 = *reinterpret_cast<const float4*>(prow0 + f);
+                    if (K > 32) a1 = *reinterpret_cast<const float4*>(prow1 + f);
+                }
+                const float a0v[4] = {a0.x, a0.y, a0.z, a0.w}, a1v[4] = {a1.x, a1.y, a1.z, a1.w};
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    const int r = 4 * g + e;
+                    dots[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v[e], acc[q][0][r], dots[0][0], 0, 0, 0);
+                    dots[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0v[e], acc[q][1][r], dots[0][1], 0, 0, 0);
+                    if (K > 32) {
+                        dots[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v[e], acc[q][0][r], dots[1][0], 0, 0, 0);
+                        dots[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v[e], acc[q][1][r], dots[1][1], 0, 0, 0);
+                    }
+                }
+            }
+        }
+    }
+
+    // red[wave][phrase][px], rn[wave, half][px], (nrmf unused), sims[phrase][px]: k_query's layout
+    const int kpad = K > 32 ? 64 : 32;
+    float* red = s_q;
+    float* rn = s_q + kQWaves * kpad * 64;
+    float* sims = rn + 2 * kQWaves * 64 + 64;
+#pragma unroll
+    for (int pt = 0; pt < 2; pt++) {
+        if (pt * 32 < kpad) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                float* o = red + (w * kpad + pt * 32 + acc_row(r, h)) * 64 + j;
+                o[0] = dots[pt][0][r];
+                o[32] = dots[pt][1][r];
+            }
+        }
+    }
+    rn[(2 * w + h) * 64 + j] = nrm[0];
+    rn[(2 * w + h) * 64 + 32 + j] = nrm[1];
+    __syncthreads();
+    const int px = tid & 63, grp = tid >> 6;
+    float n2 = rn[px];
+#pragma unroll
+    for (int i = 1; i < 2 * kQWaves; i++) n2 += rn[i * 64 + px];
+    const float nv = sqrtf(n2);
+    for (int k = grp; k < K; k += kQWaves) {
+        const float* o = red + k * 64 + px;
+        float dsum = o[0];
+#pragma unroll
+        for (int i = 1; i < kQWaves; i++) dsum += o[i * kpad * 64];
+        sims[k * 64 + px] = dsum / nv;
+    }
+    __syncthreads();
+    // one thread group scans: K <= 64 LDS reads per pixel, nothing beside the tile's MFMAs
+    if (grp != 0) return;
+    float best = sims[px];
+    int bi = 0;
+    for (int k = 1; k < K; k++) {
+        const float v = sims[k * 64 + px];
+        if (v > best) {
+            best = v;
+            bi = k;
+        }
+    }
+    const bool live = px0 + px < p.N;
+    if (live) out_label[px0 + px] = bi < p.n_pos ? bi : -1;
+    if (out_score) {
+        float sum = 0.f;
+        for (int k = 0; k < K; k++) sum += expf(10.0f * (sims[k * 64 + px] - best));
+        if (live) out_score[px0 + px] = 1.0f / sum;
+    }
+}
+
 }  // namespace
 
 static size_t query_lds_bytes(QueryParams& p)
@@ -390,6 +534,7 @@ static size_t query_lds_bytes(QueryParams& p)
     p.act_floats = act_rows * 64;
     p.ws = max_pad % 64 == 0 ? max_pad + 32 : max_pad;  // 32 mod 64: the A read's lane halves on different banks
     const int kpad = p.n_pos + p.n_neg > 32 ? 64 : 32;
+    // red, rn, nrmf, sims: either kernel's epilogue (the semantic scan adds nothing to it)
     const size_t epilogue = 4 * (size_t)(kQWaves * kpad * 64 + 2 * kQWaves * 64 + 64 + kpad * 64);
     for (int kc = 16; kc >= 4; kc >>= 1) {
         const size_t body = 4 * ((size_t)p.act_floats + 2 * (size_t)kc * p.ws);
@@ -401,28 +546,32 @@ static size_t query_lds_bytes(QueryParams& p)
     return 0;
 }
 
-hipError_t launch_query(QueryParams& p, hipStream_t s)
+hipError_t launch_query(QueryParams& p, hipStream_t s, int32_t* out_label, float* out_score)
 {
     if (p.N == 0) return hipSuccess;
+    const int sem = out_label ? 1 : 0;  // k_query_semantic
     const size_t lds = query_lds_bytes(p);
     if (lds == 0) return hipErrorInvalidValue;
     if (lds > 65536) {
         // dynamic LDS beyond the 64 KiB default is opted into once per device and size: no runtime
-        // call on a later launch's path (none inside a stream capture after a warm-up call)
+        // call on a later launch's path (none inside a stream capture after a warm-up call); each of
+        // the two kernels has its own attribute
         static std::mutex mu;
-        static size_t allowed[64] = {};
+        static size_t allowed[2][64] = {};
         int dev = 0;
         hipError_t e = hipGetDevice(&dev);
         if (e != hipSuccess) return e;
         std::lock_guard<std::mutex> lock(mu);
-        if (dev < 0 || dev >= 64 || allowed[dev] < lds) {
-            e = hipFuncSetAttribute((const void*)k_query, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (dev < 0 || dev >= 64 || allowed[sem][dev] < lds) {
+            e = hipFuncSetAttribute(sem ? (const void*)k_query_semantic : (const void*)k_query,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
-            if (dev >= 0 && dev < 64) allowed[dev] = lds;
+            if (dev >= 0 && dev < 64) allowed[sem][dev] = lds;
         }
     }
     const int64_t blocks = (p.N + kQPix - 1) / kQPix;
-    hipLaunchKernelGGL(k_query, dim3((unsigned)blocks), dim3(kQThreads), lds, s, p);
+    if (sem) hipLaunchKernelGGL(k_query_semantic, dim3((unsigned)blocks), dim3(kQThreads), lds, s, p, out_label, out_score);
+    else hipLaunchKernelGGL(k_query, dim3((unsigned)blocks), dim3(kQThreads), lds, s, p);
     return hipGetLastError();
 }
 

@@ -6,13 +6,18 @@ OpenCLIPNetwork.get_max_across (eval/openclip_encoder.py:96-112).  Here both ste
 kernel per level (include/lsr.h lsr_query_relevancy): the decoded vectors never reach HBM.  The text
 encoder stays the caller's open_clip model; its unit-norm `pos_embeds` / `neg_embeds` are passed in.
 
+get_semantic_map (eval/openclip_encoder.py:82-94), the open-vocabulary segmentation, is a second
+consumer of the same on-chip similarities (lsr_query_semantic -> semantic_map: one label per pixel and
+level, -1 where a canonical negative wins), and label_stats (lsr_label_stats) counts a label map
+against ground truth per class on the device.
+
 There is no CPU path: a CPU tensor raises.
 """
 from __future__ import annotations
 
 import ctypes
 import re
-from typing import Mapping, Optional, Sequence
+from typing import Dict, Mapping, Optional, Sequence
 
 import torch
 
@@ -102,6 +107,30 @@ def _launch(decoder: Decoder, feature: torch.Tensor, offset: int, N: int, channe
                        "lsr_query_relevancy")
 
 
+def _launch_semantic(decoder: Decoder, feature: torch.Tensor, offset: int, N: int, channel_stride: int,
+                     pixel_stride: int, phrases: torch.Tensor, n_labels: int, n_neg: int, label: torch.Tensor,
+                     label_offset: int, score: Optional[torch.Tensor] = None, score_offset: int = 0):
+    device = feature.device
+    if N == 0:
+        return
+    if decoder.packed.device != device:
+        raise ValueError("the decoder and the map must be on the same device")
+    a = _native.LsrQuerySemanticArgs()
+    a.N = N
+    a.feature = feature.data_ptr() + 4 * offset
+    a.channel_stride, a.pixel_stride = channel_stride, pixel_stride
+    a.n_layers = len(decoder.widths)
+    a.widths = decoder._widths_c
+    a.weights = decoder.packed.data_ptr()
+    a.n_labels, a.n_neg = n_labels, n_neg
+    a.phrases = phrases.data_ptr()
+    a.out_label = label.data_ptr() + 4 * label_offset
+    a.out_score = score.data_ptr() + 4 * score_offset if score is not None else None
+    with _native._on_device(device):
+        _native._check(_native.load().lsr_query_semantic(ctypes.byref(a), _native._stream(device)),
+                       "lsr_query_semantic")
+
+
 def _phrases(decoder: Decoder, pos_embeds: torch.Tensor, neg_embeds: torch.Tensor, device) -> torch.Tensor:
     # get_relevancy's torch.cat([pos, neg]).to(embed.dtype) (eval/openclip_encoder.py:44-45)
     pos = torch.as_tensor(pos_embeds).to(device=device, dtype=torch.float32)
@@ -144,6 +173,108 @@ def relevancy_map(sem_map: torch.Tensor, decoder: Decoder, pos_embeds: torch.Ten
     return out
 
 
+def semantic_map(sem_map: torch.Tensor, decoder: Decoder, label_embeds: torch.Tensor, neg_embeds: torch.Tensor,
+                 layout: str = "chw", return_score: bool = False, dtype: torch.dtype = torch.int64):
+    """OpenCLIPNetwork.get_semantic_map(Autoencoder.decode(sem_map)) -> (levels, H, W) labels: per pixel
+    the label whose embedding is most similar, -1 where one of the negatives is (the first index wins a tie).
+
+    sem_map and layout as in relevancy_map; label_embeds (n_labels, D) and neg_embeds (n_neg, D) are
+    unit-norm rows (the reference's semantic_embeds and neg_embeds).  dtype: torch.int64 (the reference's
+    .long()) or torch.int32, the kernel's own buffer without a conversion.  return_score: also the
+    (levels, H, W) fp32 softmax value of the winner.  One kernel launch per level on the current
+    stream; no host synchronisation."""
+    _require_gpu(sem_map, "semantic_map")
+    if layout not in ("chw", "hwc"):
+        raise ValueError('semantic_map: layout is "chw" or "hwc"')
+    if dtype not in (torch.int64, torch.int32):
+        raise ValueError("semantic_map: dtype is torch.int64 or torch.int32")
+    m = sem_map.detach()
+    if m.dim() == 3:
+        m = m[None]
+    c_axis = 1 if layout == "chw" else 3
+    if m.dim() != 4 or m.shape[c_axis] != 3:
+        raise ValueError(f"semantic_map: expected a (levels, 3, H, W) map (chw) or (levels, H, W, 3) (hwc), "
+                         f"got {tuple(sem_map.shape)}")
+    m = _native._f32c(m)
+    levels = int(m.shape[0])
+    H, W = (int(m.shape[2]), int(m.shape[3])) if layout == "chw" else (int(m.shape[1]), int(m.shape[2]))
+    N = H * W
+    phrases = _phrases(decoder, label_embeds, neg_embeds, m.device)
+    n_labels = int(torch.as_tensor(label_embeds).shape[0])
+    n_neg = int(phrases.shape[0]) - n_labels
+    label = torch.empty((levels, H, W), dtype=torch.int32, device=m.device)
+    score = torch.empty((levels, H, W), dtype=torch.float32, device=m.device) if return_score else None
+    cs, ps = (N, 1) if layout == "chw" else (1, 3)
+    for i in range(levels):
+        _launch_semantic(decoder, m, 3 * N * i, N, cs, ps, phrases, n_labels, n_neg, label, N * i, score, N * i)
+    if dtype != torch.int32:
+        label = label.to(dtype)
+    return (label, score) if return_score else label
+
+
+def label_stats(pred: torch.Tensor, gt: torch.Tensor, n_classes: int) -> Dict[str, torch.Tensor]:
+    """Per-class counts of predicted label maps against ground truth (include/lsr.h lsr_label_stats).
+
+    pred: (maps, H, W) integer labels, or a single (H, W) map; gt: one (H, W) map (shared by all maps)
+    or (maps, H, W).  A pixel counts only where 0 <= gt < n_classes (any other value is an
+    ignore label); a prediction outside the classes (-1) on such a pixel is a miss.  Returns
+    counts (maps, n_classes, 3) int64 = intersection, predicted, ground truth; totals (maps, 2) int64 =
+    correct, valid; iou (maps, n_classes) float64, NaN where the union is 0; miou (maps,), the mean over
+    the classes with a non-zero union; accuracy (maps,) = correct / valid.  No host synchronisation."""
+    _require_gpu(pred, "label_stats")
+    _require_gpu(gt, "label_stats")
+    if pred.device != gt.device:
+        raise ValueError("label_stats: pred and gt must be on the same device")
+    if not 1 <= int(n_classes) <= MAX_PHRASES:
+        raise ValueError(f"label_stats: n_classes is 1 to {MAX_PHRASES}")
+    if pred.dtype.is_floating_point or gt.dtype.is_floating_point:
+        raise ValueError("label_stats: pred and gt hold integer labels")
+    if pred.dim() == 2:
+        pred = pred[None]
+    if pred.dim() != 3 or tuple(gt.shape) not in (tuple(pred.shape), tuple(pred.shape[1:])):
+        raise ValueError(f"label_stats: pred is (maps, H, W) or (H, W) and gt one (H, W) map or pred's shape, "
+                         f"got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    maps = int(pred.shape[0])
+    gt_maps = maps if gt.dim() == 3 else 1
+    p = pred.detach().to(torch.int32).contiguous()
+    g = gt.detach().to(torch.int32).contiguous()
+    N = p.numel() // maps if maps else 0
+    dev = p.device
+    if maps == 0 or N == 0:  # the call enqueues nothing
+        counts = torch.zeros((maps, n_classes, 3), dtype=torch.int64, device=dev)
+        totals = torch.zeros((maps, 2), dtype=torch.int64, device=dev)
+    else:
+        counts = torch.empty((maps, n_classes, 3), dtype=torch.int64, device=dev)
+        totals = torch.empty((maps, 2), dtype=torch.int64, device=dev)
+        _label_stats_into(p, g, N, maps, gt_maps, int(n_classes), counts, totals)
+    out = {"counts": counts, "totals": totals}
+    out.update(label_metrics(counts, totals))
+    return out
+
+
+def _label_stats_into(pred: torch.Tensor, gt: torch.Tensor, N: int, maps: int, gt_maps: int, n_classes: int,
+                      counts: torch.Tensor, totals: torch.Tensor):
+    a = _native.LsrLabelStatsArgs()
+    a.N, a.n_maps, a.gt_maps, a.n_classes = N, maps, gt_maps, n_classes
+    a.pred, a.gt = pred.data_ptr(), gt.data_ptr()
+    a.out_counts, a.out_totals = counts.data_ptr(), totals.data_ptr()
+    with _native._on_device(pred.device):
+        _native._check(_native.load().lsr_label_stats(ctypes.byref(a), _native._stream(pred.device)),
+                       "lsr_label_stats")
+
+
+def label_metrics(counts: torch.Tensor, totals: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """iou, miou and accuracy (float64) from lsr_label_stats' count tensors, on their device."""
+    inter, predicted, truth = (counts[..., i].to(torch.float64) for i in range(3))
+    union = predicted + truth - inter
+    seen = union > 0
+    nan = torch.full_like(union, float("nan"))
+    iou = torch.where(seen, inter / torch.where(seen, union, torch.ones_like(union)), nan)
+    miou = torch.where(seen, iou, torch.zeros_like(iou)).sum(dim=-1) / seen.sum(dim=-1).to(torch.float64)
+    accuracy = totals[..., 0].to(torch.float64) / totals[..., 1].to(torch.float64)
+    return {"iou": iou, "miou": miou, "accuracy": accuracy}
+
+
 def decode(features: torch.Tensor, decoder: Decoder) -> torch.Tensor:
     """Autoencoder.decode of (N, 3) features -> (N, D) unit vectors, through the query kernel's
     out_decoded.  The small-N / debugging path: it writes N x D floats, which the fused query
@@ -182,3 +313,34 @@ def render_levels_relevancy(viewpoint_camera, pc, pipe, bg_color, opt, language_
                             scaling_modifier=scaling_modifier)
         pkg["relevancy"] = relevancy_map(pkg["language_feature_images"], decoder, pos_embeds, neg_embeds)
     return pkg
+
+
+def _put_semantic(pkg, images, decoder, label_embeds, neg_embeds, return_score, dtype):
+    got = semantic_map(images, decoder, label_embeds, neg_embeds, return_score=return_score, dtype=dtype)
+    if return_score:
+        pkg["semantic"], pkg["semantic_score"] = got
+    else:
+        pkg["semantic"] = got
+    return pkg
+
+
+def render_semantic(viewpoint_camera, pc, pipe, bg_color, opt, decoder: Decoder, label_embeds, neg_embeds,
+                    scaling_modifier=1.0, return_score=False, dtype=torch.int64):
+    """render_relevancy's forward followed by semantic_map on its language_feature_image: the render
+    package plus "semantic", (1, H, W) labels, and with return_score "semantic_score", (1, H, W)."""
+    from .render import render
+    with torch.no_grad():
+        pkg = render(viewpoint_camera, pc, pipe, bg_color, opt, scaling_modifier=scaling_modifier)
+        return _put_semantic(pkg, pkg["language_feature_image"], decoder, label_embeds, neg_embeds, return_score, dtype)
+
+
+def render_levels_semantic(viewpoint_camera, pc, pipe, bg_color, opt, language_features, decoder: Decoder,
+                           label_embeds, neg_embeds, scaling_modifier=1.0, return_score=False, dtype=torch.int64):
+    """levels.render_levels followed by semantic_map on every level's map: the render_levels package
+    plus "semantic", (L, H, W) labels, and with return_score "semantic_score", (L, H, W)."""
+    from .levels import render_levels
+    with torch.no_grad():
+        pkg = render_levels(viewpoint_camera, pc, pipe, bg_color, opt, language_features,
+                            scaling_modifier=scaling_modifier)
+        return _put_semantic(pkg, pkg["language_feature_images"], decoder, label_embeds, neg_embeds, return_score,
+                             dtype)
