@@ -928,12 +928,24 @@ int32_t lsr_levels_step_backward(const lsr_settings* settings, const lsr_levels_
  *     4 T      the forward's scheduled tiles, class by class
  *     4 R      the num_rendered point-list entries
  * i.e. what LSR_PHASE_COMPOSITE[_FILLED], lsr_backward (with or without geometry gradients) and
- * lsr_language_tail read of the geometry phase's products.  Sort and scan scratch, depth keys and
- * super-tile tables are not kept, nor what the compositing writes (cover bytes, split states, the
- * backward's work lists, final_T, n_contrib), nor the records' language slots.
+ * lsr_language_tail read of the geometry phase's products (lsr_view_pack_bytes: a pack may end here),
+ * and then, in a pack of at least lsr_view_plan_pack_bytes, the view's WALK PLAN: what a compositing
+ * of that geometry derives from the geometry alone (the same bits at every visit while the geometry
+ * is frozen) and is worth keeping,
+ *     R        the instances' cover masks
+ * The plan is valid if a render forward that writes a backward's state (not LSR_FWD_NO_BACKWARD) ran
+ * on the set between its geometry call and lsr_view_save -- counter word 8 says so: the render forward
+ * sets it, the geometry phase clears it, and lsr_view_save keeps it with the pack.  A pack saved
+ * before any compositing has the segments (the size does not depend on it) but no plan, and a pack
+ * of fewer than lsr_view_plan_pack_bytes has neither: both bind as the plain bound form.
+ * lsr_view_restore ignores the plan.  Sort and scan scratch, depth keys and super-tile tables are not
+ * kept, nor what else the compositing writes (split states, the backward's work lists, final_T,
+ * n_contrib, loss codes: it writes them at every step), nor the records' language slots.
+ * lsr_view_plan_layout gives the plan segment's offset.
  *
  * lsr_view_save reads a buffer set that a capacity-mode LSR_PHASE_GEOMETRY forward filled (the
- * compositing and backward of that view may have run on it since) whose view fitted its capacities;
+ * compositing and backward of that view may have run on it since: nothing after the render forward
+ * rewrites the cover masks -- the backward only reads them) whose view fitted its capacities;
  * num_rendered is that view's count (counter slot 1, read back by the caller).  lsr_view_restore
  * brings a set into the state that geometry call would leave, for everything a later phase reads;
  * it also re-initialises what the geometry phase clears on every run and a later phase relies on:
@@ -964,6 +976,30 @@ typedef struct lsr_view_args {
     int32_t* overflow;            /* restore: NULL, or the forward's overflow flag (set to 0) */
 } lsr_view_args;
 size_t lsr_view_pack_bytes(int32_t P, int32_t width, int32_t height, int64_t num_rendered);
+/* Bytes of a pack that also holds the view's walk plan (see above); 0 for what lsr_view_pack_bytes
+ * answers with 0. */
+size_t lsr_view_plan_pack_bytes(int32_t P, int32_t width, int32_t height, int64_t num_rendered);
+/* Byte offsets of the walk plan: its segment in a pack of num_rendered instances (pack_cover;
+ * pack_bytes = lsr_view_plan_pack_bytes) and the array it is saved from in a buffer set of
+ * capacity_rendered (set_cover, in the binning buffer; the flag word word_plan_ready of the counters at
+ * set_counters in the image buffer).  TEST SUPPORT, not an interface to build on: the set_* fields are a
+ * set's internal layout and may change with any library build; no caller needs them to use the plan
+ * (lsr_view_plan_pack_bytes, lsr_view_save and lsr_view_bind are the interface).  For tests that compare
+ * a hit with a miss it also says where the set
+ * keeps the rest of what a compositing leaves for the backward, none of it part of the plan:
+ * set_final_T, set_n_contrib, set_split_desc, set_bwd_lists and set_loss_code (the fused loss's
+ * per-pixel code bytes) in the image buffer.  The backward's lists: class c (0 .. classes - 1) holds
+ * counters[word_bwd_class + c] items at set_bwd_lists + 4 c split_items tiles.
+ * Host only (no device work).  Both added without a change of
+ * LSR_ABI_VERSION (the smaller pack and every earlier call behave as before): a library that has
+ * these symbols keeps and binds walk plans. */
+typedef struct lsr_view_plan_offsets {
+    size_t pack_counters, pack_cover, pack_bytes;
+    size_t set_counters, set_cover, set_final_T, set_n_contrib, set_split_desc, set_bwd_lists, set_loss_code;
+    size_t tiles, classes, split_items, word_plan_ready, word_bwd_class;
+} lsr_view_plan_offsets;
+int32_t lsr_view_plan_layout(int32_t P, int32_t width, int32_t height, int64_t capacity_rendered, int64_t num_rendered,
+                             lsr_view_plan_offsets* out);
 /* The eight counter slots a capacity-mode geometry call left in `image` (the set's LSR_BUF_IMAGE
  * buffer of a width x height forward; slot 1 = num_rendered, slot 7 = the overflow word) into
  * host_counters: 8 x uint32 of pinned host memory the device can write, by one one-wave kernel on
@@ -978,9 +1014,11 @@ int32_t lsr_view_restore(const lsr_view_args* args, void* stream);
  * lsr_view_restore copies a pack (78 MB at 1M Gaussians and 1080p) into the set at every revisit.
  * The bound form leaves the large arrays where they are.  Every buffer set carries, at the end of its
  * geometry buffer (lsr_view_bind_layout; lsr_geom_bytes includes both),
- *   - a table of 32 bytes: { const float4* rec01; const float4* recb; const uint32_t* point_list;
- *     uint32_t s01, sb; } -- Gaussian i's two leading record words at rec01[s01 i], rec01[s01 i + 1],
- *     its third word {b, f0, f1, f2} at recb[sb i];
+ *   - a table of 48 bytes: { const float4* rec01; const float4* recb; const uint32_t* point_list;
+ *     uint32_t s01, sb; const uint8_t* cover; uint32_t plan, pad; } -- Gaussian i's two leading record
+ *     words at rec01[s01 i], rec01[s01 i + 1], its third word {b, f0, f1, f2} at recb[sb i]; the walk
+ *     plan's cover masks when plan != 0 (the set is bound to a pack with a plan), else null (the
+ *     kernels use the set's own array);
  *   - a plane of P float4 {b, f0, f1, f2}: the home of the language slots in this form.
  * A render forward made with LSR_BIND_FORWARD in lsr_forward_args.flags and a lsr_backward made with
  * LSR_BIND_BACKWARD in lsr_backward_args.flags read the table once per workgroup and gather the
@@ -1002,6 +1040,13 @@ int32_t lsr_view_restore(const lsr_view_args* args, void* stream);
  *     lsr_view_restore does.  About 30 MB of traffic at 1M Gaussians and 1080p instead of 157 MB.
  *     The pack is only read: several sets may be bound to one pack at once, and the caller keeps it
  *     alive until the last composite / backward of every set bound to it has finished.
+ *     If the pack holds a walk plan (decided on the device, from the pack's counter word 8, so one
+ *     captured composite + backward serves packs with and without): the table names the pack's cover
+ *     masks.  The render forward then reads each instance's mask from the pack instead of computing
+ *     it, and stores none; the backward reads the masks through the table.  Every output is what a
+ *     miss produces (the gradients up to the order of their float atomics).  The masks are those of
+ *     the geometry alone, so a plan serves any later composite / backward of that view, with or
+ *     without split replay.
  *   - lsr_view_bind with args->pack == NULL (num_rendered and pack_bytes ignored): the identity
  *     table, and b from the set's records into plane[i].x, for a set whose geometry phase ran
  *     without LSR_BIND_FORWARD.

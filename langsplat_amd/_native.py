@@ -109,6 +109,14 @@ class LsrStateLayout(ctypes.Structure):
         "counters", "ranges", "final_T", "n_contrib", "point_list", "grad_records")]
 
 
+class LsrViewPlanOffsets(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_size_t) for n in (
+        "pack_counters", "pack_cover", "pack_bytes",
+        "set_counters", "set_cover", "set_final_T", "set_n_contrib", "set_split_desc", "set_bwd_lists",
+        "set_loss_code",
+        "tiles", "classes", "split_items", "word_plan_ready", "word_bwd_class")]
+
+
 class LsrKernelStat(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 32), ("launches", ctypes.c_int64), ("total_ms", ctypes.c_double)]
 
@@ -207,6 +215,9 @@ SIGNATURES = {
     "lsr_rgb_loss_forward": (ctypes.c_int32, [ctypes.POINTER(LsrRgbLossArgs), _vp]),
     "lsr_rgb_loss_backward": (ctypes.c_int32, [ctypes.POINTER(LsrRgbLossBwdArgs), _vp]),
     "lsr_view_pack_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
+    "lsr_view_plan_pack_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]),
+    "lsr_view_plan_layout": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                              ctypes.c_int64, ctypes.POINTER(LsrViewPlanOffsets)]),
     "lsr_view_counts": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int32, _vp, _vp, _vp]),
     "lsr_view_save": (ctypes.c_int32, [ctypes.POINTER(LsrViewArgs), _vp]),
     "lsr_view_restore": (ctypes.c_int32, [ctypes.POINTER(LsrViewArgs), _vp]),
@@ -250,6 +261,8 @@ SIGNATURES = {
 # the bound form of the view cache (include/lsr.h lsr_view_bind): added without an ABI bump, so a
 # library of the same ABI may lack them; has_view_bind() says whether they are there
 OPTIONAL = ("lsr_view_bind_layout", "lsr_view_bind", "lsr_fill_language_plane", "lsr_adam_fill_language_plane")
+# the walk plan (include/lsr.h lsr_view_plan_pack_bytes), additive in the same way: has_view_plan()
+OPTIONAL_PLAN = ("lsr_view_plan_pack_bytes", "lsr_view_plan_layout")
 BIND_FORWARD, BIND_BACKWARD, BIND_FILL_PLANE, BIND_CLAMPED = 16, 16, 32, 1
 
 _lib: Optional[ctypes.CDLL] = None
@@ -265,7 +278,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         _build.build()
     lib = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
-        if name in OPTIONAL and not hasattr(lib, name):
+        if name in OPTIONAL + OPTIONAL_PLAN and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.restype = res
@@ -1175,6 +1188,26 @@ def fill_language(language_feature: torch.Tensor, raw: int, radii: torch.Tensor,
 def view_pack_bytes(P: int, W: int, H: int, num_rendered: int) -> int:
     """Bytes of a view pack (include/lsr.h lsr_view_pack_bytes)."""
     return int(load().lsr_view_pack_bytes(int(P), int(W), int(H), int(num_rendered)))
+
+
+def has_view_plan() -> bool:
+    """The library keeps a view's walk plan in packs of view_plan_pack_bytes (include/lsr.h)."""
+    lib = load()
+    return all(hasattr(lib, n) for n in OPTIONAL_PLAN)
+
+
+def view_plan_pack_bytes(P: int, W: int, H: int, num_rendered: int) -> int:
+    """Bytes of a view pack with room for the walk plan (include/lsr.h lsr_view_plan_pack_bytes)."""
+    return int(load().lsr_view_plan_pack_bytes(int(P), int(W), int(H), int(num_rendered)))
+
+
+def view_plan_layout(P: int, W: int, H: int, capacity_rendered: int, num_rendered: int) -> Dict[str, int]:
+    """Byte offsets of the walk plan's segments in a pack and of the set's arrays they are saved from
+    (include/lsr.h lsr_view_plan_layout)."""
+    lay = LsrViewPlanOffsets()
+    _check(load().lsr_view_plan_layout(int(P), int(W), int(H), int(capacity_rendered), int(num_rendered),
+                                       ctypes.byref(lay)), "lsr_view_plan_layout")
+    return {name: int(getattr(lay, name)) for name, _ in LsrViewPlanOffsets._fields_}
 
 
 def view_args(buffers: "static_buffers", num_rendered: int, pack: torch.Tensor) -> LsrViewArgs:

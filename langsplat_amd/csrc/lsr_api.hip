@@ -1104,7 +1104,39 @@ int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_allo
 size_t lsr_view_pack_bytes(int32_t P, int32_t width, int32_t height, int64_t num_rendered)
 {
     if (P < 1 || width < 1 || height < 1 || num_rendered < 0) return 0;
+    return make_view_pack(P, width, height, num_rendered).geometry_bytes;
+}
+
+size_t lsr_view_plan_pack_bytes(int32_t P, int32_t width, int32_t height, int64_t num_rendered)
+{
+    if (P < 1 || width < 1 || height < 1 || num_rendered < 0) return 0;
     return make_view_pack(P, width, height, num_rendered).bytes;
+}
+
+int32_t lsr_view_plan_layout(int32_t P, int32_t width, int32_t height, int64_t capacity_rendered, int64_t num_rendered,
+                             lsr_view_plan_offsets* out)
+{
+    if (P < 1 || width < 1 || height < 1 || capacity_rendered < 1 || num_rendered < 0 ||
+        num_rendered > capacity_rendered || !out)
+        return fail(LSR_ERR_INVALID, "lsr_view_plan_layout: invalid argument");
+    const ViewPack V = make_view_pack(P, width, height, num_rendered);
+    const Layout L = make_layout(P, width, height, capacity_rendered, 0);
+    out->pack_counters = V.counters;
+    out->pack_cover = V.cover;
+    out->pack_bytes = V.bytes;
+    out->set_counters = L.counters;
+    out->set_cover = L.cover;
+    out->set_final_T = L.final_T;
+    out->set_n_contrib = L.n_contrib;
+    out->set_split_desc = L.split_desc;
+    out->set_bwd_lists = L.tile_lists + 4 * (size_t)kWorkClasses * (size_t)L.tiles;
+    out->set_loss_code = L.loss_code;
+    out->tiles = (size_t)L.tiles;
+    out->classes = kWorkClasses;
+    out->split_items = kSplitItems;
+    out->word_plan_ready = kCntPlanReady;
+    out->word_bwd_class = kCntBwdClass;
+    return LSR_OK;
 }
 
 int32_t lsr_view_counts(int32_t width, int32_t height, const void* image, uint32_t* host_counters, void* stream_ptr)
@@ -1161,6 +1193,7 @@ static int32_t view_copy(const lsr_view_args* a, void* stream_ptr, bool restore)
     v.pack = static_cast<char*>(a->pack);
     v.radii = a->radii;
     v.overflow = restore ? a->overflow : nullptr;
+    v.plan_room = a->pack_bytes >= lsr_view_plan_pack_bytes(a->P, a->width, a->height, a->num_rendered);
     // counters[kCntFwdFlags] as forward_impl publishes it
     v.fwd_flags = ((a->flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) |
                   (a->fused_loss ? kFwdFusedLoss : 0u) | ((a->flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) |
@@ -1223,6 +1256,7 @@ int32_t lsr_view_bind(const lsr_view_args* a, int32_t bind_flags, void* stream_p
     v.pack = static_cast<char*>(a->pack);
     v.radii = a->radii;
     v.overflow = a->pack ? a->overflow : nullptr;
+    v.plan_room = a->pack && a->pack_bytes >= lsr_view_plan_pack_bytes(a->P, a->width, a->height, a->num_rendered);
     v.fwd_flags = ((a->flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) |
                   (a->fused_loss ? kFwdFusedLoss : 0u) | ((a->flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) |
                   ((a->flags & LSR_FWD_NO_BACKWARD) ? kFwdNoBackward : 0u);

@@ -19,6 +19,8 @@ enum Counter : int {
     kCntKeyMin = 5,      // smallest visible depth key (float bits)
     kCntKeyMax = 6,      // largest visible depth key
     kCntOverflow = 7,    // capacity mode: the view exceeds the caller's capacities (nothing is binned)
+    kCntPlanReady = 8,   // a compositing wrote this geometry's cover masks into the set (the geometry phase
+                         // clears it, as every word it does not publish): lsr_view_save keeps it with the pack
     kCntSlots = 16
 };
 constexpr uint32_t kFwdZeroedRecords = 1u;  // the language step's gradient records cleared (the render
@@ -78,13 +80,20 @@ constexpr int kDepthScans = 5;         // 4 depth-sort passes + the instance-off
 // the table's address, so one captured composite + backward serves every view.  Gaussian i's two
 // leading record words are rec01[s01 i], rec01[s01 i + 1] (the set's records: s01 = 3; a pack's rec01
 // segment: 2), its third word {b, f0, f1, f2} is recb[sb i] (the set's records: 3; the plane: 1).
+// The walk plan (plan != 0: a hit on a pack that holds one, include/lsr.h): the instances' cover masks,
+// which the compositing derives from the geometry alone, read from the pack by both render kernels
+// instead of being computed, stored and read back; plan == 0 (a miss, or a pack saved before any
+// compositing): cover is null and the kernels use their arguments' array.
 struct ViewBind {
     const float4* rec01;
     const float4* recb;
     const uint32_t* point_list;
     uint32_t s01, sb;
+    const uint8_t* cover;
+    uint32_t plan, pad;
 };
-static_assert(sizeof(ViewBind) == 32, "two 16-byte words");
+static_assert(sizeof(ViewBind) == 48, "three 16-byte words");
+constexpr uint32_t kPlanOn = 1u;  // ViewBind::plan: cover is the pack's
 
 struct Layout {
     // geometry (per Gaussian)
@@ -532,7 +541,10 @@ hipError_t launch_label_stats(const lsr_label_stats_args& a, hipStream_t s);
 // 16-byte aligned (include/lsr.h lsr_view_pack_bytes documents the sizes)
 constexpr int kViewCounterWords = kCntSlots + kWorkClasses;  // the slots and the forward's class counts
 struct ViewPack {
-    size_t counters, rec01, recb, radii, clamped, ranges, order, point_list, bytes;
+    size_t counters, rec01, recb, radii, clamped, ranges, order, point_list;
+    size_t geometry_bytes;  // a pack without room for the walk plan ends here (lsr_view_pack_bytes)
+    // the walk plan (valid when the saved counters' kCntPlanReady is set)
+    size_t cover, bytes;
 };
 inline ViewPack make_view_pack(int P, int W, int H, int64_t R)
 {
@@ -549,6 +561,8 @@ inline ViewPack make_view_pack(int P, int W, int H, int64_t R)
     V.ranges = take(8 * T);
     V.order = take(4 * T);
     V.point_list = take(4 * r);
+    V.geometry_bytes = o;
+    V.cover = take(r);
     V.bytes = o;
     return V;
 }
@@ -559,6 +573,7 @@ struct ViewParams {
     int32_t* radii;
     int32_t* overflow;   // restore: the caller's flag (0 afterwards), or null
     uint32_t fwd_flags;  // restore: counters[kCntFwdFlags] as the geometry call would publish it
+    bool plan_room;      // the pack has room for the walk plan (pack_bytes >= make_view_pack().bytes)
 };
 // one launch: the set's kept state into the pack, or (restore) back, with the words the geometry phase
 // clears on every run

@@ -169,7 +169,7 @@ __global__ __launch_bounds__(kPreThreads) void k_preprocess(PreprocessParams p)
     for (int w = i; w < p.zero_words; w += gridDim.x * blockDim.x) p.zero[w] = 0u;
     for (int w = i; w < p.zero2_words; w += gridDim.x * blockDim.x) p.zero2[w] = 0u;
     if (p.bind && i == 0) {  // the bound form, a cache miss: the table names the set's own arrays
-        ViewBind t;
+        ViewBind t{};  // (no walk plan: plan = 0)
         t.rec01 = p.record;
         t.recb = p.plane;
         t.point_list = p.bind_point_list;

@@ -307,7 +307,9 @@ __device__ __forceinline__ TilePixel tile_pixel(const RenderParams& p, int tile,
 // Stages the list entry with the gathered records a, b, c in batch slot t: the three records every
 // walk reads, then more() (the caller's records: the feature's rest, further levels), then the
 // entry's cover mask, which is returned.  The order of the LDS stores and the cover test is the
-// training kernel's register budget: leave it.
+// training kernel's register budget: leave it.  k_render_forward's walk-plan branch repeats the three
+// record stores by hand (it has the mask already; sharing them through a helper changed the benched
+// kernel's instruction order): a change to them here is made there too.
 template <class More>
 __device__ __forceinline__ uint8_t stage_entry(float4* sA, float4* sB, float4* sC, uint8_t* sM, int t, const float4 a,
                                                const float4 b, const float4 c, float tx0, float ty0,
@@ -469,6 +471,21 @@ __device__ __forceinline__ BoundView bound_view(const RenderParams& p)
     v.s01 = t->s01;
     v.sb = t->sb;
     return v;
+}
+
+// The walk plan of a bound set (ViewBind::plan, lsr_view_bind of a pack that holds one): the
+// instances' cover masks are the pack's, as the view's first compositing left them -- a function of
+// the frozen geometry alone.  plan 0 (not bound, a miss, or a pack without a plan): the arguments' own
+// array, which the forward writes and the backward reads.
+// Read like bound_view: scalar loads from a uniform address, issued where a value is needed.
+__device__ __forceinline__ uint32_t plan_flags(const RenderParams& p)
+{
+    return p.bind ? ((const LSR_CONSTANT ViewBind*)p.bind)->plan : 0u;
+}
+__device__ __forceinline__ LSR_GLOBAL const uint8_t* plan_cover(const RenderParams& p)
+{
+    const uint8_t* c = p.bind ? ((const LSR_CONSTANT ViewBind*)p.bind)->cover : nullptr;
+    return (LSR_GLOBAL const uint8_t*)(c ? c : p.cover);
 }
 
 // The language feature of one pixel composited by a scalar front-to-back walk over the whole tile
@@ -673,6 +690,12 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
     uint32_t bi = 0;                              // batch index
 
     const int T = p.gx * p.gy;
+    // the set's walk plan (plan_cover), read from the table wherever it is tested: a scalar load from a
+    // uniform address, not a value held across the walk
+    auto planned = [&] { return plan_flags(p) != 0u; };
+    // this launch leaves the geometry's cover masks in the set (lsr_view_save keeps the word with the
+    // pack); not on a hit, which stores none
+    if (blockIdx.x == 0 && threadIdx.x == 0 && p.sched_counts && !p.no_bwd && !planned()) p.sched_counts[kCntPlanReady] = 1u;
     if (p.zero_records) {  // the backward's gradient records: stores beside the VALU-bound walk
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int64_t k = (int64_t)blockIdx.x * kThreads + threadIdx.x; k < p.zero_records_n4;
@@ -728,11 +751,13 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
             ph.st[3] = wall_clock64();
         }
         a = b = c = make_float4(0.f, 0.f, 0.f, 0.f);
+        uint8_t m_plan = 0;  // planned: the instance's cover mask from the pack (coalesced: one byte per thread)
         if (idx < end) {
             const uint32_t g = g_next;
             a = vb.word01(g, 0);
             b = vb.word01(g, 1);
             c = vb.word2(g);
+            if (planned()) m_plan = plan_cover(p)[idx];
         }
         if (kStats && base == start) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -754,9 +779,17 @@ __global__ __launch_bounds__(kTilePixels, kFwdWaves) void k_render_forward(Rende
             nrec++;
         }
         if (idx < end) {
-            const uint8_t m = stage_entry(sA, sB, sC, sM, t, a, b, c, tx0, ty0,
-                                          [&] { sF[t] = make_float4(c.z, c.w, 0.0f, 0.0f); });
-            if (!p.no_bwd) p.cover[idx] = m;  // for the backward (coalesced: one byte per thread)
+            if (planned()) {  // stage_entry's record stores without its cover test: keep the two alike
+                sA[t] = make_float4(a.x, a.y, -0.5f * a.z, -0.5f * b.x);
+                sB[t] = make_float4(a.w, b.y, power_cutoff(b.y), 0.0f);
+                sC[t] = make_float4(b.z, b.w, c.x, c.y);
+                sF[t] = make_float4(c.z, c.w, 0.0f, 0.0f);
+                sM[t] = m_plan;
+            } else {
+                const uint8_t m = stage_entry(sA, sB, sC, sM, t, a, b, c, tx0, ty0,
+                                              [&] { sF[t] = make_float4(c.z, c.w, 0.0f, 0.0f); });
+                if (!p.no_bwd) p.cover[idx] = m;  // for the backward (coalesced: one byte per thread)
+            }
         }
         __syncthreads();
         if (kStats) {
@@ -1619,7 +1652,8 @@ __global__ __launch_bounds__(kTilePixels) void k_render_backward(RenderParams p)
             const uint32_t live = (k < w0 ? 1u : 0u) | (k < w1 ? 2u : 0u) | (k < w2 ? 4u : 0u) | (k < w3 ? 8u : 0u);
             // the forward's mask of this instance (it loaded every instance below any pixel's
             // contributor count): the same function of the same inputs, not recomputed
-            cover = (uint32_t)p.cover[start + k] & live;
+            // (a bound set with a walk plan: the pack's copy)
+            cover = (uint32_t)plan_cover(p)[start + k] & live;
         }
         sM[t] = (uint8_t)cover;
         for (int i = t; i < kThreads * kGS; i += kThreads) sG[i] = 0.f;

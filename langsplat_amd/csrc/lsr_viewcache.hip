@@ -22,9 +22,15 @@
 //              class, each class in its list's order (workgroup b's tile, and with it the order in
 //              which the fused loss adds the workgroups' shares, is what it was)
 //   point_list the num_rendered entries
-// Not kept: depth keys, sort and scan scratch, super-tile tables (geometry-internal); cover bytes,
-// split states, the backward's class counts and lists, final_T, n_contrib, loss codes (the compositing
-// writes them); the language slots; the gradient records (cleared by the compositing or the backward).
+// and the walk plan, which a view's first compositing derives from that geometry alone and which is
+// still in the set when the set is next visited (nothing between the render forward and that visit
+// rewrites it: the backward only reads it):
+//   cover      the R instances' cover masks (entry_cover)
+// valid when the saved counters' kCntPlanReady is set (the render forward sets it, the geometry phase
+// clears it): a pack saved before any compositing has no plan, and binds as the plain bound form.
+// Not kept: depth keys, sort and scan scratch, super-tile tables (geometry-internal); split states,
+// the backward's class counts and lists, final_T, n_contrib, loss codes (the compositing writes them
+// at every step); the language slots; the gradient records (cleared by the compositing or the backward).
 #include "lsr_internal.h"
 
 namespace lsr {
@@ -35,7 +41,8 @@ constexpr int kViewThreads = 256;
 // the guides' cap for memory-bound grids on this chip (256 CUs x 8 blocks), grid-stride beyond
 constexpr int kViewMaxBlocks = 2048;
 
-enum ViewSeg : int { kSegRecord, kSegPointList, kSegRadii, kSegClamped, kSegRanges, kSegOrder, kSegCounters, kSegLoss, kSegs };
+// (kSegCover, the walk plan: save only, into a pack with room for it)
+enum ViewSeg : int { kSegRecord, kSegPointList, kSegRadii, kSegClamped, kSegRanges, kSegOrder, kSegCounters, kSegLoss, kSegCover, kSegs };
 
 struct ViewCopy {
     size_t end[kSegs];  // running ends of the segments' item ranges
@@ -60,6 +67,9 @@ struct ViewCopy {
     uint4* pk_ranges;
     uint32_t* pk_order;
     uint4* pk_point_list;
+    // the walk plan
+    uint4 *cover, *pk_cover;
+    int plan_room;  // the pack has the plan's segment (else it ends after the point list)
 };
 
 template <bool kRestore, typename T>
@@ -152,12 +162,14 @@ __global__ __launch_bounds__(kViewThreads) void k_view_copy(ViewCopy p)
             move_order<kRestore>(p, (uint32_t)(i - p.end[kSegRanges]));
         } else if (i < p.end[kSegCounters]) {
             const int c = (int)(i - p.end[kSegOrder]);
-            if (!kRestore)
-                p.pk_counters[c] = p.counters[c];
+            if (!kRestore)  // (a pack without room for the plan says it has none)
+                p.pk_counters[c] = c == kCntPlanReady && !p.plan_room ? 0u : p.counters[c];
             else
                 restore_counter(p, c);
-        } else {  // restore: the fused loss's words start at 0 (the preprocess clears them)
+        } else if (i < p.end[kSegLoss]) {  // restore: the fused loss's words start at 0 (the preprocess clears them)
             p.loss_words[i - p.end[kSegCounters]] = make_uint4(0u, 0u, 0u, 0u);
+        } else {  // (save only)
+            move<kRestore>(p.cover, p.pk_cover, i - p.end[kSegLoss]);
         }
     }
 }
@@ -165,15 +177,22 @@ __global__ __launch_bounds__(kViewThreads) void k_view_copy(ViewCopy p)
 // lsr_view_bind.  Segment kSegRecord is the plane's b word (one Gaussian per item), kSegPointList the
 // table (one item); the other segments are k_view_copy<true>'s.  identity (no pack): the table names
 // the set's own arrays and b comes from the set's records; only those two segments have items.
+// With a pack that holds a walk plan (its counters' kCntPlanReady, read here: one capture serves packs
+// with and without), the table also names the pack's cover masks.
 __global__ __launch_bounds__(kViewThreads) void k_view_bind(ViewCopy p, float4* plane, ViewBind* bind, int identity)
 {
     const size_t stride = (size_t)gridDim.x * kViewThreads;
+    const bool plan = !identity && p.plan_room && p.pk_counters[kCntPlanReady] != 0u;
     for (size_t i = (size_t)blockIdx.x * kViewThreads + threadIdx.x; i < p.end[kSegs - 1]; i += stride) {
         if (i < p.end[kSegRecord]) {  // .x only: the language slots .yzw belong to the feature fill
             const float b = identity ? reinterpret_cast<const float*>(p.record + 3 * i + 2)[0] : p.pk_recb[i];
             reinterpret_cast<float*>(plane + i)[0] = b;
         } else if (i < p.end[kSegPointList]) {
-            ViewBind t;
+            ViewBind t{};
+            if (plan) {
+                t.cover = reinterpret_cast<const uint8_t*>(p.pk_cover);
+                t.plan = kPlanOn;
+            }
             t.rec01 = identity ? p.record : p.pk_rec01;
             t.s01 = identity ? 3u : 2u;
             t.recb = plane;
@@ -236,6 +255,9 @@ static ViewCopy view_copy_params(const ViewParams& v, const Layout& L)
     p.pk_ranges = reinterpret_cast<uint4*>(v.pack + V.ranges);
     p.pk_order = reinterpret_cast<uint32_t*>(v.pack + V.order);
     p.pk_point_list = reinterpret_cast<uint4*>(v.pack + V.point_list);
+    p.cover = reinterpret_cast<uint4*>(v.binning + L.cover);
+    p.pk_cover = reinterpret_cast<uint4*>(v.pack + V.cover);
+    p.plan_room = v.plan_room ? 1 : 0;
     return p;
 }
 
@@ -259,6 +281,8 @@ hipError_t launch_view_copy(const ViewParams& v, bool restore, hipStream_t s)
     p.end[kSegOrder] = n += T;
     p.end[kSegCounters] = n += restore ? (size_t)kCntWords : (size_t)kViewCounterWords;
     p.end[kSegLoss] = n += restore ? (T + 1) / 2 : 0;
+    // (the array is padded past a whole number of 16-byte words, in the set and in the pack)
+    p.end[kSegCover] = n += !restore && v.plan_room ? (R + 15) / 16 : 0;
     const dim3 grid = view_grid(n);
     if (restore)
         hipLaunchKernelGGL(k_view_copy<true>, grid, dim3(kViewThreads), 0, s, p);
@@ -284,6 +308,7 @@ hipError_t launch_view_bind(const ViewParams& v, bool clamped, hipStream_t s)
     p.end[kSegOrder] = n += identity ? 0 : T;
     p.end[kSegCounters] = n += identity ? 0 : (size_t)kCntWords;
     p.end[kSegLoss] = n += identity ? 0 : (T + 1) / 2;
+    p.end[kSegCover] = n;
     hipLaunchKernelGGL(k_view_bind, view_grid(n), dim3(kViewThreads), 0, s, p, reinterpret_cast<float4*>(v.geom + L.lang_plane),
                        reinterpret_cast<ViewBind*>(v.geom + L.view_bind), identity ? 1 : 0);
     return hipGetLastError();

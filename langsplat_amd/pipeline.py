@@ -106,6 +106,8 @@ class ViewCache:
         native.pack_bytes(num_rendered) -> int         bytes of a pack of that many tile instances
         native.alloc(nbytes) -> pack                   device memory for one pack
         native.save(r, num_rendered, pack)             set r's geometry into the pack (stream B)
+        native.pack_bytes_without_plan(num_rendered)   optional: a smaller pack, tried when pack_bytes'
+                                                       (which has room for the view's walk plan) is over budget
         native.restore(r, num_rendered, pack)          the pack into set r (stream B)
 
     and, for the bound form (include/lsr.h lsr_view_bind: the set reads the pack in place),
@@ -188,6 +190,11 @@ class ViewCache:
             if int(host[self.OVERFLOW]) == 0:
                 rendered = int(host[self.RENDERED])
                 nbytes = self.native.pack_bytes(rendered)
+                small = getattr(self.native, "pack_bytes_without_plan", None)
+                if self.bytes + nbytes > self.budget and small is not None:
+                    # no room for the view's walk plan: a pack that ends after the geometry (a hit on
+                    # it is the plain bound form) still saves the geometry phase
+                    nbytes = small(rendered)
                 if self.bytes + nbytes <= self.budget:
                     pack = self.native.alloc(nbytes)
                     self.native.save(r, rendered, pack)
@@ -244,6 +251,12 @@ class _ViewNative:
         self.dims = (call["P"], call["W"], call["H"])
 
     def pack_bytes(self, rendered):
+        # bound: with room for the view's walk plan, which a hit then reads in place too
+        if self.bound and _native.has_view_plan():
+            return _native.view_plan_pack_bytes(*self.dims, rendered)
+        return _native.view_pack_bytes(*self.dims, rendered)
+
+    def pack_bytes_without_plan(self, rendered):
         return _native.view_pack_bytes(*self.dims, rendered)
 
     def alloc(self, nbytes):
