@@ -4,7 +4,8 @@ TEST INFRASTRUCTURE ONLY (see oracle/lsr_oracle.c header).  Where lsr_oracle.c r
 upstream kernels line by line (per-pixel loops, hand-derived backward with T recovered by
 division), this file writes the same model as dense tensor algebra per tile -- alpha matrix,
 cumulative-product transmittance, termination mask -- and lets torch.autograd derive every
-gradient.  Agreement of the two (tests/test_torch_reference.py) pins the oracle's hand-written
+gradient.  Agreement of the two (tests/test_oracle_render.py, tests/test_oracle_cameras.py,
+tests/test_oracle_value_edges.py) pins the oracle's hand-written
 backward and the compositing semantics; both follow SURVEY.md Appendix A and the reference call
 site gaussian_renderer/__init__.py:19-115.
 

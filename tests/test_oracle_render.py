@@ -1,5 +1,7 @@
 """Oracle rendering: analytic known-answer cases and agreement with the
-independent dense-autograd restatement (oracle/torch_ref.py), forward and backward."""
+independent dense-autograd restatement (oracle/torch_ref.py), forward and backward.  The same
+comparison under rolled, close-in and off-screen cameras: tests/test_oracle_cameras.py; on scenes
+at the value edges of the blend and the activations: tests/test_oracle_value_edges.py."""
 import math
 
 import numpy as np
