@@ -731,7 +731,8 @@ int32_t lsr_rgb_loss_backward(const lsr_rgb_loss_bwd_args* args, void* stream);
  * The extra levels' activated features of the visible Gaussians are staged in one scratch array,
  * requested as LSR_BUF_LEVELS (P > 0 and levels > 1 only): ceil(3 (levels - 1) / 4) float4 per
  * Gaussian, {l1.0 l1.1 l1.2 l2.0}{l2.1 l2.2 l3.0 l3.1}{l3.2 - - -}, so a list entry's gather is whole
- * 16-byte loads.  lsr_levels_bytes is exactly that request (0 for levels == 1 or P <= 0).
+ * 16-byte loads.  lsr_levels_bytes is exactly that request: the array's size rounded up to 256 bytes
+ * (0 for levels == 1 or P <= 0).
  *
  * Refused with LSR_ERR_INVALID before any device work, the message naming the field: levels outside
  * 1..LSR_MAX_LEVELS; reserved != 0; settings.include_feature == 0; fwd.flags != LSR_FWD_NO_BACKWARD;
@@ -779,8 +780,8 @@ int32_t lsr_debug_levels_occupancy(int32_t levels);
  * LSR_RAW_LANGUAGE (the normalisation's chain rule per level; language_feature is read only then),
  * else w.r.t. the activated features; exact zeros for culled Gaussians (radii <= 0).  With P == 0
  * nothing is written; with num_rendered == 0 or all-zero seeds the output is zeros.  `scratch` is
- * lsr_backward_levels_bytes(P, levels) bytes (P rows of 3 levels floats; 0 for P <= 0 or levels outside
- * 1..LSR_MAX_LEVELS), cleared by the call itself.  The call enqueues its work on `stream` and never
+ * lsr_backward_levels_bytes(P, levels) bytes (P rows of 3 levels floats, rounded up to 256 bytes; 0 for
+ * P <= 0 or levels outside 1..LSR_MAX_LEVELS), cleared by the call itself.  The call enqueues its work on `stream` and never
  * waits for the device.  The sums are float atomic adds: the last bits depend on arrival order.
  *
  * Refused with LSR_ERR_INVALID before any device work, the message naming the field: a NULL settings

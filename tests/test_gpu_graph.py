@@ -69,7 +69,9 @@ def test_capacity_mode_matches_eager(P, W, H):
 @pytest.mark.parametrize("short", ["rendered", "entries"])
 def test_capacity_overflow_is_flagged_and_safe(short):
     """A view over capacity: flagged, background image, zero contributors -- and the next forward
-    with room is exact again (nothing was written out of bounds)."""
+    with room is exact again (that nothing was written out of bounds is checked with guarded,
+    capacity-sized buffers by tests/test_gpu_write_extent.py
+    test_capacity_mode_stays_inside_capacity_sized_buffers)."""
     P, W, H = 4000, 128, 96
     st, inp = scene(P=P, W=W, H=H, seed=6, scale_range=(0.03, 0.2), bg=(0.25, 0.5, 0.75))
     std, ind = to_device(st, inp, DEV)

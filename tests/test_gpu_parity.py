@@ -91,9 +91,10 @@ def assert_grad_close(name, gpu, ref, outliers=0.0):
     ref = np.asarray(ref, dtype=np.float64)
     assert gpu.shape == ref.shape, name
     floor = GRAD_FLOOR * (np.max(np.abs(ref)) if ref.size else 0.0) + 1e-30
-    bad = np.abs(gpu - ref) > GRAD_RTOL * (np.abs(ref) + floor)
+    # (not `>`: a NaN -- a sum started from uninitialised records, say -- compares false both ways)
+    bad = ~(np.abs(gpu - ref) <= GRAD_RTOL * (np.abs(ref) + floor))
     if outliers > 0.0 and bad.sum() <= outliers * bad.size:
-        bad = np.abs(gpu - ref) > 10 * GRAD_RTOL * (np.abs(ref) + floor)
+        bad = ~(np.abs(gpu - ref) <= 10 * GRAD_RTOL * (np.abs(ref) + floor))
     if bad.any():
         i = np.argmax(np.abs(gpu - ref) / (np.abs(ref) + floor))
         raise AssertionError(f"{name}: {bad.sum()} / {bad.size} entries off; worst gpu={gpu.flat[i]} "
