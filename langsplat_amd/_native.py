@@ -791,6 +791,42 @@ def check_level_features(language_features, P: int) -> int:
     return int(language_features.shape[0])
 
 
+def _fill_levels_forward_args(la: LsrForwardLevelsArgs, means3D, shs, colors_precomp, lf, opacities, scales, rotations,
+                              cov3D_precomp, raw, shs_rest, color, langs, radii, visible):
+    """lsr_forward_levels_args of either levels forward: the inference forward of level 0 (lf[0] into
+    langs[0]) and, with more than one level, the rest of the contiguous (L, P, 3) stack lf and of langs."""
+    _fill_forward_args(la.fwd, means3D, shs, colors_precomp, lf, opacities, scales, rotations, cov3D_precomp, raw,
+                       FWD_NO_BACKWARD, shs_rest, color, langs, radii, visible)
+    la.levels = int(lf.shape[0])
+    if la.levels > 1:
+        la.more_language_feature = _ptr(lf[1:])
+        la.more_out_language_feature = _ptr(langs[1:])
+
+
+def _fill_levels_backward_args(who: str, a, keep: list, L, H, W, radii, geom, binning, image, grad_images, images,
+                               targets, masks, grad_losses):
+    """The seeds (validated; ValueError in who's name), the forward's state buffers and radii of either
+    levels backward's args struct; the tensors the call reads are appended to keep."""
+    fused = [images, targets, masks, grad_losses]
+    if any(x is not None for x in fused) and any(x is None for x in fused):
+        raise ValueError(f"{who}: images, targets, masks and grad_losses go together")
+    if grad_images is None and images is None:
+        raise ValueError(f"{who}: no seed (grad_images or the fused seed)")
+    for name, t in (("grad_images", grad_images), ("images", images), ("targets", targets)):
+        if t is not None and tuple(t.shape) != (L, 3, H, W):
+            raise ValueError(f"{who}: {name} must be ({L}, 3, {H}, {W}), got {tuple(t.shape)}")
+    if grad_images is not None:
+        keep.append(_f32c(grad_images.detach()))
+        a.dL_dout_language_feature = keep[-1].data_ptr()
+    if images is not None:
+        if masks.dtype != torch.bool or tuple(masks.shape) != (L, H, W) or tuple(grad_losses.shape) != (L,):
+            raise ValueError(f"{who}: masks must be ({L}, {H}, {W}) bool and grad_losses ({L},)")
+        keep += [_f32c(images.detach()), _f32c(targets.detach()), masks.contiguous(), _f32c(grad_losses.detach())]
+        a.out_language_feature, a.loss_target, a.loss_mask, a.dL_dloss = (t.data_ptr() for t in keep[-4:])
+    a.geom_buffer, a.binning_buffer, a.image_buffer = _ptr(geom), _ptr(binning), _ptr(image)
+    a.radii = _ptr(radii)
+
+
 def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_features, opacities, scales, rotations,
                                cov3D_precomp, raw=0, shs_rest=None, with_visibility=False, keep_state=False):
     """All language levels of a scene in one inference forward (include/lsr.h lsr_forward_levels):
@@ -813,12 +849,8 @@ def rasterize_gaussians_levels(rs, means3D, shs, colors_precomp, language_featur
     radii = torch.empty((P,), dtype=torch.int32, device=device)  # preprocess writes every entry
     visible = torch.empty((P,), dtype=torch.bool, device=device) if with_visibility else None
     la = LsrForwardLevelsArgs()
-    _fill_forward_args(la.fwd, means3D, shs, colors_precomp, lf, opacities, scales, rotations, cov3D_precomp, raw,
-                       FWD_NO_BACKWARD, shs_rest, color, langs, radii, visible)
-    la.levels = L
-    if L > 1:
-        la.more_language_feature = _ptr(lf[1:])
-        la.more_out_language_feature = _ptr(langs[1:])
+    _fill_levels_forward_args(la, means3D, shs, colors_precomp, lf, opacities, scales, rotations, cov3D_precomp, raw,
+                              shs_rest, color, langs, radii, visible)
     entries = ctypes.c_int64(0)
     la.fwd.out_num_entries = ctypes.pointer(entries)
     alloc = _Allocator(device)
@@ -850,32 +882,14 @@ def rasterize_gaussians_levels_backward(rs, language_features, radii, num_render
     H, W = int(rs.image_height), int(rs.image_width)
     keep: list = []
     s = make_settings(rs, keep)
-    fused = [images, targets, masks, grad_losses]
-    if any(x is not None for x in fused) and any(x is None for x in fused):
-        raise ValueError("rasterize_gaussians_levels_backward: images, targets, masks and grad_losses go together")
-    if grad_images is None and images is None:
-        raise ValueError("rasterize_gaussians_levels_backward: no seed (grad_images or the fused seed)")
     a = LsrBackwardLevelsArgs()
+    _fill_levels_backward_args("rasterize_gaussians_levels_backward", a, keep, L, H, W, radii, geom, binning, image,
+                               grad_images, images, targets, masks, grad_losses)
     a.P, a.levels, a.raw, a.num_rendered = P, L, int(raw) & RAW_LANGUAGE, int(num_rendered)
     lf = _f32c(language_features.detach())
     a.language_feature = _ptr(lf)
-    for name, t in (("grad_images", grad_images), ("images", images), ("targets", targets)):
-        if t is not None and tuple(t.shape) != (L, 3, H, W):
-            raise ValueError(f"rasterize_gaussians_levels_backward: {name} must be ({L}, 3, {H}, {W}), got "
-                             f"{tuple(t.shape)}")
-    if grad_images is not None:
-        keep.append(_f32c(grad_images.detach()))
-        a.dL_dout_language_feature = keep[-1].data_ptr()
-    if images is not None:
-        if masks.dtype != torch.bool or tuple(masks.shape) != (L, H, W) or tuple(grad_losses.shape) != (L,):
-            raise ValueError(f"rasterize_gaussians_levels_backward: masks must be ({L}, {H}, {W}) bool and "
-                             f"grad_losses ({L},)")
-        keep += [_f32c(images.detach()), _f32c(targets.detach()), masks.contiguous(), _f32c(grad_losses.detach())]
-        a.out_language_feature, a.loss_target, a.loss_mask, a.dL_dloss = (t.data_ptr() for t in keep[-4:])
     out = torch.empty((L, P, 3), dtype=torch.float32, device=device)
     scratch = torch.empty((int(lib.lsr_backward_levels_bytes(P, L)),), dtype=torch.uint8, device=device)
-    a.geom_buffer, a.binning_buffer, a.image_buffer = _ptr(geom), _ptr(binning), _ptr(image)
-    a.radii = _ptr(radii)
     a.scratch = _ptr(scratch)
     a.dL_dlanguage_feature = _ptr(out)
     with _on_device(device):
@@ -911,12 +925,8 @@ def levels_step_forward(rs, means3D, shs, colors_precomp, language_features, opa
     visible = output_tensor("visible", (P,), torch.bool, device)
     sa = LsrLevelsStepForwardArgs()
     la = sa.levels
-    _fill_forward_args(la.fwd, means3D, shs, colors_precomp, lf, opacities, scales, rotations, cov3D_precomp, raw,
-                       FWD_NO_BACKWARD, shs_rest, color, langs, radii, visible)
-    la.levels = L
-    if L > 1:
-        la.more_language_feature = _ptr(lf[1:])
-        la.more_out_language_feature = _ptr(langs[1:])
+    _fill_levels_forward_args(la, means3D, shs, colors_precomp, lf, opacities, scales, rotations, cov3D_precomp, raw,
+                              shs_rest, color, langs, radii, visible)
     la.fwd.phase = forward_phase.active()
     la.fwd.capacity_rendered = cap.rendered
     la.fwd.capacity_entries = cap.entries
@@ -974,12 +984,9 @@ def levels_step_backward(rs, language_features, radii, num_rendered, geom, binni
     H, W = int(rs.image_height), int(rs.image_width)
     keep: list = []
     s = make_settings(rs, keep)
-    fused = [images, targets, masks, grad_losses]
-    if any(x is not None for x in fused) and any(x is None for x in fused):
-        raise ValueError("levels_step_backward: images, targets, masks and grad_losses go together")
-    if grad_images is None and images is None:
-        raise ValueError("levels_step_backward: no seed (grad_images or the fused seed)")
     a = LsrLevelsStepBackwardArgs()
+    _fill_levels_backward_args("levels_step_backward", a, keep, L, H, W, radii, geom, binning, image, grad_images,
+                               images, targets, masks, grad_losses)
     a.P, a.levels, a.raw, a.num_rendered = P, L, int(raw) & RAW_LANGUAGE, int(num_rendered)
     if update is not None:
         if language_features is not update.param and language_features.data_ptr() != update.param.data_ptr():
@@ -988,17 +995,6 @@ def levels_step_backward(rs, language_features, radii, num_rendered, geom, binni
     else:
         lf = _f32c(language_features.detach())
     a.language_feature = _ptr(lf)
-    for name, t in (("grad_images", grad_images), ("images", images), ("targets", targets)):
-        if t is not None and tuple(t.shape) != (L, 3, H, W):
-            raise ValueError(f"levels_step_backward: {name} must be ({L}, 3, {H}, {W}), got {tuple(t.shape)}")
-    if grad_images is not None:
-        keep.append(_f32c(grad_images.detach()))
-        a.dL_dout_language_feature = keep[-1].data_ptr()
-    if images is not None:
-        if masks.dtype != torch.bool or tuple(masks.shape) != (L, H, W) or tuple(grad_losses.shape) != (L,):
-            raise ValueError(f"levels_step_backward: masks must be ({L}, {H}, {W}) bool and grad_losses ({L},)")
-        keep += [_f32c(images.detach()), _f32c(targets.detach()), masks.contiguous(), _f32c(grad_losses.detach())]
-        a.out_language_feature, a.loss_target, a.loss_mask, a.dL_dloss = (t.data_ptr() for t in keep[-4:])
     if out is None and (want_grad or update is None):
         out = torch.empty((L, P, 3), dtype=torch.float32, device=device)
     nbytes = int(lib.lsr_backward_levels_bytes(P, L))
@@ -1008,8 +1004,6 @@ def levels_step_backward(rs, language_features, radii, num_rendered, geom, binni
         raise ValueError(f"levels_step_backward: scratch must be a uint8 tensor of at least {nbytes} bytes")
     if out is not None and (tuple(out.shape) != (L, P, 3) or out.dtype != torch.float32 or not out.is_contiguous()):
         raise ValueError(f"levels_step_backward: out must be a contiguous fp32 ({L}, {P}, 3) tensor")
-    a.geom_buffer, a.binning_buffer, a.image_buffer = _ptr(geom), _ptr(binning), _ptr(image)
-    a.radii = _ptr(radii)
     a.scratch = _ptr(scratch)
     a.dL_dlanguage_feature = _ptr(out)
     if update is not None:

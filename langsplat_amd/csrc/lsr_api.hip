@@ -13,6 +13,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "lsr_internal.h"
@@ -218,16 +219,20 @@ hipError_t wait_counters(const HostBlock* hb, uint32_t seq, hipStream_t stream)
 }
 }  // namespace
 
-static int32_t fail(int32_t code, const char* what, hipError_t e = hipSuccess)
+// who: the entry point's name where a check is shared; the text is then "<who>: <what>"
+static int32_t fail(int32_t code, const char* what, hipError_t e = hipSuccess, const char* who = nullptr)
 {
     char buf[512];
+    const int at = who ? snprintf(buf, sizeof(buf), "%s: ", who) : 0;
     if (e != hipSuccess)
-        snprintf(buf, sizeof(buf), "%s: %s (%s)", what, hipGetErrorString(e), hipGetErrorName(e));
+        snprintf(buf + at, sizeof(buf) - at, "%s: %s (%s)", what, hipGetErrorString(e), hipGetErrorName(e));
     else
-        snprintf(buf, sizeof(buf), "%s", what);
+        snprintf(buf + at, sizeof(buf) - at, "%s", what);
     g_last_error = buf;
     return code;
 }
+
+static int32_t invalid(const char* who, const char* what) { return fail(LSR_ERR_INVALID, what, hipSuccess, who); }
 
 #define LSR_TRY(expr, what)                                                  \
     do {                                                                     \
@@ -256,6 +261,40 @@ static AdamScalars adam_scalars(double lr, double beta1, double beta2, double ep
     return a;
 }
 
+// the hyper-parameters of a device-side step (step_dev): t.step is the tensor's offset from the device count
+static AdamHyper adam_hyper(const lsr_adam_tensor& t) { return AdamHyper{t.lr, t.beta1, t.beta2, t.eps, t.step}; }
+
+// counters[kCntFwdFlags]: what a forward with these lsr_forward_flags prepared (fused_loss: it wrote the
+// loss codes).  Published by the forward, and by lsr_view_restore / lsr_view_bind standing in for one.
+static uint32_t forward_flags_word(int32_t flags, bool fused_loss)
+{
+    return ((flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) | (fused_loss ? kFwdFusedLoss : 0u) |
+           ((flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) | ((flags & LSR_FWD_NO_BACKWARD) ? kFwdNoBackward : 0u);
+}
+
+// The RenderParams fields every walk over a forward's lists reads, from the forward's three buffers (the
+// levels gradient walk reads only the size, ranges, point_list, record and the schedule).  The caller adds
+// what is its own: outputs, seeds, bind, loss, split and zero-records settings.
+static RenderParams walk_params(int W, int H, const Layout& L, char* geom, char* image, char* binning)
+{
+    RenderParams rp{};
+    rp.W = W;
+    rp.H = H;
+    rp.gx = L.gx;
+    rp.gy = L.gy;
+    rp.ranges = reinterpret_cast<const uint2*>(image + L.ranges);
+    rp.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
+    rp.cover = reinterpret_cast<uint8_t*>(binning + L.cover);
+    rp.record = reinterpret_cast<const float4*>(geom + L.record);
+    rp.final_T = reinterpret_cast<float*>(image + L.final_T);
+    rp.n_contrib = reinterpret_cast<uint32_t*>(image + L.n_contrib);
+    rp.sched_counts = reinterpret_cast<uint32_t*>(image + L.counters);
+    rp.sched_lists = reinterpret_cast<uint32_t*>(image + L.tile_lists);
+    rp.split_pool = reinterpret_cast<float*>(image + L.split_pool);
+    rp.split_desc = reinterpret_cast<uint4*>(image + L.split_desc);
+    return rp;
+}
+
 // lsr_forward_levels' additions to a forward: the extra levels' inputs and outputs, and the level
 // array (LSR_BUF_LEVELS) once it is allocated
 struct LevelsCall {
@@ -267,27 +306,17 @@ struct LevelsCall {
 
 // The gradient walk of lsr_backward_levels and lsr_levels_step_backward (A: either args struct, validated
 // by its entry point; P > 0, num_rendered > 0): clears the accumulator (a->scratch) and adds every
-// level's per-Gaussian sums to it.
+// level's per-Gaussian sums to it; epilogue: then the accumulator -> a->dL_dlanguage_feature.
 template <class A>
-static int32_t levels_grad_walk(const lsr_settings* s, const A* a, hipStream_t stream, bool debug)
+static int32_t levels_grad_walk(const lsr_settings* s, const A* a, hipStream_t stream, bool debug, bool epilogue)
 {
     const int P = a->P, W = s->image_width, H = s->image_height, levels = a->levels;
     const Layout L = make_layout(P, W, H, a->num_rendered, 0);  // point_list sits at offset 0
-    char* geom = static_cast<char*>(a->geom_buffer);
-    char* image = static_cast<char*>(a->image_buffer);
-    char* binning = static_cast<char*>(a->binning_buffer);
     float* acc = static_cast<float*>(a->scratch);
     LSR_TRY(zero_fill(acc, sizeof(float) * 3 * (size_t)levels * (size_t)P, stream), "memset levels grad");
     LevelsGradParams gp{};
-    gp.r.W = W;
-    gp.r.H = H;
-    gp.r.gx = L.gx;
-    gp.r.gy = L.gy;
-    gp.r.ranges = reinterpret_cast<const uint2*>(image + L.ranges);
-    gp.r.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
-    gp.r.record = reinterpret_cast<const float4*>(geom + L.record);
-    gp.r.sched_counts = reinterpret_cast<uint32_t*>(image + L.counters);
-    gp.r.sched_lists = reinterpret_cast<uint32_t*>(image + L.tile_lists);
+    gp.r = walk_params(W, H, L, static_cast<char*>(a->geom_buffer), static_cast<char*>(a->image_buffer),
+                       static_cast<char*>(a->binning_buffer));
     gp.levels = levels;
     gp.dL_dout = a->dL_dout_language_feature;
     gp.out_lang = a->out_language_feature;
@@ -296,6 +325,11 @@ static int32_t levels_grad_walk(const lsr_settings* s, const A* a, hipStream_t s
     gp.dL_dloss = a->dL_dloss;
     gp.acc = acc;
     LSR_TRY(launch_render_levels_grad(gp, L.tiles, stream), "render levels grad");
+    if (epilogue)
+        LSR_TRY(launch_levels_grad_epilogue(P, levels, a->radii, acc,
+                                            (a->raw & LSR_RAW_LANGUAGE) ? a->language_feature : nullptr,
+                                            a->dL_dlanguage_feature, stream),
+                "levels grad epilogue");
     return LSR_OK;
 }
 
@@ -305,25 +339,10 @@ static int32_t render_forward_and_finish(const lsr_settings* s, const lsr_forwar
                                          const LevelsCall* lv = nullptr)
 {
     const int P = a->P, W = s->image_width, H = s->image_height;
-    (void)P;
-    RenderParams rp{};
-    rp.W = W;
-    rp.H = H;
-    rp.gx = L.gx;
-    rp.gy = L.gy;
+    RenderParams rp = walk_params(W, H, L, geom, image, binning);
     rp.include_feature = (s->include_feature && a->language_feature) ? 1 : 0;
-    rp.ranges = reinterpret_cast<const uint2*>(image + L.ranges);
-    rp.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
-    rp.cover = reinterpret_cast<uint8_t*>(binning + L.cover);
-    rp.record = reinterpret_cast<const float4*>(geom + L.record);
     if (a->flags & LSR_BIND_FORWARD) rp.bind = reinterpret_cast<const ViewBind*>(geom + L.view_bind);
     rp.bg = s->bg;
-    rp.final_T = reinterpret_cast<float*>(image + L.final_T);
-    rp.n_contrib = reinterpret_cast<uint32_t*>(image + L.n_contrib);
-    rp.sched_counts = reinterpret_cast<uint32_t*>(image + L.counters);
-    rp.sched_lists = reinterpret_cast<uint32_t*>(image + L.tile_lists);
-    rp.split_pool = reinterpret_cast<float*>(image + L.split_pool);
-    rp.split_desc = reinterpret_cast<uint4*>(image + L.split_desc);
     rp.out_color = a->out_color;
     rp.out_lang = a->out_language_feature;
     rp.split_color = (a->flags & LSR_FWD_NO_COLOR_GRAD) ? 0 : 1;
@@ -359,11 +378,436 @@ static int32_t render_forward_and_finish(const lsr_settings* s, const lsr_forwar
     return LSR_OK;
 }
 
+// The deferred language feature (lsr_forward_args.language_ready): the feature's update (another
+// stream) has overlapped everything enqueued so far; the stream waits for it, then the visible
+// Gaussians' records receive the feature.  Inside a graph capture the event is one recorded in the
+// same capture (a join of the two branches).
+static hipError_t wait_and_fill_language(const lsr_forward_args* a, const Layout& L, char* geom, hipStream_t stream)
+{
+    hipError_t e = hipStreamWaitEvent(stream, static_cast<hipEvent_t>(a->language_ready), 0);
+    if (e != hipSuccess) return e;
+    return launch_fill_language(a->P, a->language_feature, a->raw, a->radii, reinterpret_cast<float4*>(geom + L.record),
+                                stream);
+}
+
+// forward_impl's argument checks (their order is part of the contract: the first fault answers); also
+// clears *a->out_num_entries, before the fused-loss check
+static int32_t check_forward_args(const lsr_settings* s, const lsr_forward_args* a, const LevelsCall* lv)
+{
+    const int P = a->P, W = s->image_width, H = s->image_height;
+    if (P < 0 || W <= 0 || H <= 0 || W > 65535 * kTile || H > 65535 * kTile)
+        return fail(LSR_ERR_INVALID, "lsr_forward: invalid P or image size");
+    if (s->sh_degree < 0 || s->sh_degree > 3) return fail(LSR_ERR_INVALID, "lsr_forward: sh_degree must be 0..3");
+    if (!a->out_color || !a->out_language_feature || (P > 0 && (!a->radii || !a->means3D || !a->opacities)))
+        return fail(LSR_ERR_INVALID, "lsr_forward: missing input/output pointer");
+    if (P > 0 && (!a->shs) == (!a->colors_precomp))
+        return fail(LSR_ERR_INVALID, "lsr_forward: provide exactly one of shs / colors_precomp");
+    if (P > 0 && ((a->scales && a->rotations) ? 1 : 0) == (a->cov3D_precomp ? 1 : 0))
+        return fail(LSR_ERR_INVALID, "lsr_forward: provide exactly one of scales+rotations / cov3D_precomp");
+    if (a->shs && (a->M < (s->sh_degree + 1) * (s->sh_degree + 1)))
+        return fail(LSR_ERR_INVALID, "lsr_forward: M smaller than (sh_degree+1)^2");
+    if (!s->bg || !s->viewmatrix || !s->projmatrix || !s->campos)
+        return fail(LSR_ERR_INVALID, "lsr_forward: settings tensors missing");
+    if (a->raw & ~(LSR_RAW_OPACITY | LSR_RAW_SCALES | LSR_RAW_ROTATIONS | LSR_RAW_LANGUAGE))
+        return fail(LSR_ERR_INVALID, "lsr_forward: unknown raw flag");
+    if (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD | LSR_BIND_FORWARD))
+        return fail(LSR_ERR_INVALID, "lsr_forward: unknown flag");
+    if ((a->flags & LSR_BIND_FORWARD) && (a->phase == LSR_PHASE_ALL || lv))
+        return fail(LSR_ERR_INVALID, "lsr_forward: LSR_BIND_FORWARD needs a forward phase (capacity mode) of lsr_forward");
+    if (a->shs_rest && (!a->shs || a->M < 2))
+        return fail(LSR_ERR_INVALID, "lsr_forward: shs_rest needs shs (features_dc) and M >= 2");
+    if (a->capacity_rendered < 0 || (a->capacity_rendered > 0 && a->capacity_entries <= 0) ||
+        a->capacity_rendered > 0xFFFFFFFFll || a->capacity_entries > 0xFFFFFFFFll)
+        return fail(LSR_ERR_INVALID, "lsr_forward: capacity mode needs capacity_rendered > 0 and capacity_entries > 0 "
+                                     "(both < 2^32)");
+    if (a->phase < LSR_PHASE_ALL || a->phase > LSR_PHASE_COMPOSITE_FILLED ||
+        (a->phase != LSR_PHASE_ALL && (a->capacity_rendered <= 0 || a->language_ready)))
+        return fail(LSR_ERR_INVALID, "lsr_forward: a forward phase needs capacity mode and no language_ready");
+    if (a->out_num_entries) *a->out_num_entries = 0;
+    if (a->out_loss && (!s->include_feature || (P > 0 && !a->language_feature) || !a->loss_target || !a->loss_mask))
+        return fail(LSR_ERR_INVALID, "lsr_forward: the fused loss needs include_feature, language_feature, "
+                                     "loss_target and loss_mask");
+    return LSR_OK;
+}
+
+// P == 0: upstream leaves the images at their zero initialisation when there is nothing to draw
+static int32_t forward_empty_scene(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
+                                   hipStream_t stream, bool debug, const LevelsCall* lv)
+{
+    const int W = s->image_width, H = s->image_height;
+    const size_t HW = (size_t)W * H;
+    LSR_TRY(zero_fill(a->out_color, 3 * HW * 4, stream), "memset color");
+    LSR_TRY(zero_fill(a->out_language_feature, 3 * HW * 4, stream), "memset language");
+    if (lv) LSR_TRY(zero_fill(lv->out_more, (size_t)(lv->levels - 1) * 3 * HW * 4, stream), "memset language");
+    if (a->out_loss) {
+        const Layout L0 = make_layout(0, W, H, 0, 0);
+        char* image = static_cast<char*>(alloc(user, LSR_BUF_IMAGE, L0.image_bytes));
+        if (!image) return fail(LSR_ERR_ALLOC, "lsr_forward: image buffer allocation failed");
+        RenderParams rp{};
+        rp.W = W;
+        rp.H = H;
+        rp.loss_gt = a->loss_target;
+        rp.loss_mask = a->loss_mask;
+        rp.loss_code = reinterpret_cast<uint8_t*>(image + L0.loss_code);
+        rp.loss_partial = reinterpret_cast<double*>(image + L0.loss_partial);
+        rp.out_loss = a->out_loss;
+        LSR_TRY(launch_loss_background(rp, stream), "loss");
+    }
+    return LSR_OK;
+}
+
+// The preprocess of a forward into its geometry buffer (L: make_layout(P, W, H, 0, 0)).  The caller adds
+// the placed emission's count table and the bound form's plane and table.
+static PreprocessParams preprocess_params(const lsr_settings* s, const lsr_forward_args* a, const Layout& L, char* geom,
+                                          uint32_t* counters)
+{
+    const int W = s->image_width, H = s->image_height;
+    PreprocessParams pp{};
+    pp.P = a->P;
+    pp.M = a->M;
+    pp.D = s->sh_degree;
+    pp.W = W;
+    pp.H = H;
+    pp.gx = L.gx;
+    pp.gy = L.gy;
+    pp.tanfovx = s->tanfovx;
+    pp.tanfovy = s->tanfovy;
+    pp.focal_y = (float)H / (2.0f * s->tanfovy);
+    pp.focal_x = (float)W / (2.0f * s->tanfovx);
+    pp.scale_modifier = s->scale_modifier;
+    pp.include_feature = s->include_feature;
+    pp.prefiltered = s->prefiltered;
+    pp.means = a->means3D;
+    pp.shs = a->shs;
+    pp.colors = a->colors_precomp;
+    pp.lang = a->language_feature;
+    pp.opac = a->opacities;
+    pp.scales = a->scales;
+    pp.rots = a->rotations;
+    pp.cov_pre = a->cov3D_precomp;
+    pp.view = s->viewmatrix;
+    pp.proj = s->projmatrix;
+    pp.campos = s->campos;
+    pp.radii = a->radii;
+    pp.visible = a->visible;
+    pp.depth_key = reinterpret_cast<uint32_t*>(geom + L.depth_key);
+    pp.tiles = reinterpret_cast<uint32_t*>(geom + L.tiles_touched);
+    pp.rect = reinterpret_cast<uint32_t*>(geom + L.rect);
+    pp.clamped = reinterpret_cast<uint32_t*>(geom + L.clamped);
+    pp.record = reinterpret_cast<float4*>(geom + L.record);
+    pp.counters = counters;
+    pp.zero = reinterpret_cast<uint32_t*>(geom + L.scan_regions);
+    pp.zero_words = (int)L.zero_words;  // depth-sort scan status and the fused loss's words
+    pp.raw = a->raw;
+    pp.shs_rest = a->shs_rest;
+    pp.partial = reinterpret_cast<uint4*>(geom + L.pre_partial);
+    return pp;
+}
+
+// What forward_impl's common setup hands to its three paths.
+struct ForwardCall {
+    const lsr_settings* s;
+    const lsr_forward_args* a;
+    lsr_alloc_fn alloc;
+    void* user;
+    hipStream_t stream;
+    bool debug;
+    int64_t* num_rendered;
+    LevelsCall* lv;
+    Layout L;  // make_layout(P, W, H, 0, 0): the geometry and image buffers' (each path sizes its binning)
+    HostBlock* hb;
+    char *geom, *image;
+    uint32_t* counters;
+    bool placed;    // placed emission (the MSD depth order's fused emission at super-tile-major positions)
+    bool deferred;  // geometry first, the language feature after the caller's event or in the composite call
+};
+
+// capacity mode's entry capacity: the MSD depth order's fused emission holds at most L.fused_cap entries
+static int64_t entry_capacity(const lsr_forward_args* a, const Layout& L)
+{
+    return !depth_order_uses_pass_count(a->P) ? std::min<int64_t>(a->capacity_entries, L.fused_cap) : a->capacity_entries;
+}
+
+// LSR_PHASE_COMPOSITE / LSR_PHASE_COMPOSITE_FILLED: the geometry call's buffers (same allocator keys and
+// sizes): the feature (unless a fused update already wrote it, LSR_PHASE_COMPOSITE_FILLED), then the
+// compositing
+static int32_t forward_composite(const ForwardCall& f)
+{
+    const lsr_forward_args* a = f.a;
+    hipStream_t stream = f.stream;
+    const bool debug = f.debug, bound = (a->flags & LSR_BIND_FORWARD) != 0;
+    const int P = a->P;
+    const int64_t R_cap = a->capacity_rendered;
+    const Layout L = make_layout(P, f.s->image_width, f.s->image_height, R_cap, entry_capacity(a, f.L));
+    char* binning = static_cast<char*>(f.alloc(f.user, LSR_BUF_BINNING, L.binning_bytes));
+    if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
+    *f.num_rendered = R_cap;
+    if (f.deferred && a->phase == LSR_PHASE_COMPOSITE) {
+        LSR_TRY(launch_fill_language(P, a->language_feature, a->raw, a->radii,
+                                     reinterpret_cast<float4*>(f.geom + (bound ? L.lang_plane : L.record)), stream,
+                                     bound ? 1 : 0),
+                "fill language");
+        if (f.lv)
+            LSR_TRY(launch_fill_levels(P, f.lv->levels, f.lv->more, a->raw, a->radii, f.lv->lev, stream), "fill levels");
+    }
+    return render_forward_and_finish(f.s, a, L, f.geom, f.image, binning, f.hb, stream, debug, f.lv);
+}
+
+// Capacity mode, after the preprocess: nothing waits for the device.  The counters stay on the device, the
+// binning's grids and buffers come from the capacities and its kernels read the true counts; a view over
+// capacity sets counters[kCntOverflow] (and *overflow) and is not binned.  binning: the bound form's,
+// taken before the preprocess, else null.
+static int32_t forward_capacity(const ForwardCall& f, uint4* partial, uint32_t fwd_flags, char* binning)
+{
+    const lsr_forward_args* a = f.a;
+    hipStream_t stream = f.stream;
+    const bool debug = f.debug;
+    HostBlock* hb = f.hb;
+    const int P = a->P;
+    const int64_t R_cap = a->capacity_rendered;
+    const bool fused = !depth_order_uses_pass_count(P);
+    const int64_t E_cap = entry_capacity(a, f.L);
+    // LSD order (large P): the passes this thread's last eager forward needed (its key range is
+    // not read on the host here; a view that needs more is flagged as over capacity)
+    const int passes = fused ? 0 : (hb->depth_passes > 0 ? hb->depth_passes : 4);
+    LSR_TRY(launch_publish_counters((P + kPreThreads - 1) / kPreThreads, partial, f.counters, nullptr, 0, fwd_flags,
+                                    (uint32_t)R_cap, (uint32_t)E_cap, a->overflow, passes, stream),
+            "publish counters");
+    LSR_TRY(launch_depth_order(P, fused ? 4 : passes, f.L, f.geom, f.counters, &hb->stall, stream, debug, fused,
+                               (uint32_t)E_cap, f.placed),
+            "depth order");
+    const Layout L = make_layout(P, f.s->image_width, f.s->image_height, R_cap, E_cap);
+    if (!binning) binning = static_cast<char*>(f.alloc(f.user, LSR_BUF_BINNING, L.binning_bytes));
+    if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
+    LSR_TRY(launch_binning(P, R_cap, L, f.geom, f.image, binning, &hb->stall, stream, debug, fused,
+                           DevCount{f.counters + kCntSuper, f.counters + kCntOverflow}, f.placed),
+            "binning");
+    *f.num_rendered = R_cap;
+    if (a->phase == LSR_PHASE_GEOMETRY) return LSR_OK;
+    if (f.deferred) LSR_TRY(wait_and_fill_language(a, L, f.geom, stream), "fill language");
+    // (lsr_levels_step_forward, one phase: level 0 went into the records in the preprocess)
+    if (f.lv) LSR_TRY(launch_fill_levels(P, f.lv->levels, f.lv->more, a->raw, a->radii, f.lv->lev, stream), "fill levels");
+    return render_forward_and_finish(f.s, a, L, f.geom, f.image, binning, hb, stream, debug, f.lv);
+}
+
+// The eager forward, after the preprocess, with the one host wait: num_rendered R and the super-tile
+// entries E size the binning buffer, and the visible depth-key range fixes the number of depth-sort
+// passes.  The depth sort is enqueued BEFORE the wait, with this thread's last pass count: it reads the
+// key range on the device, and any pass count >= the needed one gives the same order (the extra digits are
+// all 0), so the GPU sorts while the host waits, instead of idling until the host has enqueued the next
+// launch.  Should the range need more passes than guessed, the sort is run again below.
+static int32_t forward_eager(const ForwardCall& f, uint4* partial, uint32_t fwd_flags, HostMarks& hm)
+{
+    const lsr_settings* s = f.s;
+    const lsr_forward_args* a = f.a;
+    hipStream_t stream = f.stream;
+    const bool debug = f.debug, placed = f.placed;
+    HostBlock* hb = f.hb;
+    LevelsCall* lv = f.lv;
+    char *geom = f.geom, *image = f.image;
+    uint32_t* counters = f.counters;
+    const int P = a->P, W = s->image_width, H = s->image_height;
+    const uint32_t seq = ++hb->seq == 0 ? ++hb->seq : hb->seq;
+    LSR_TRY(launch_publish_counters((P + kPreThreads - 1) / kPreThreads, partial, counters, hb->slot, seq, fwd_flags, 0u,
+                                    0u, nullptr, 0, stream),
+            "publish counters");
+    const int guess = hb->depth_passes > 0 ? hb->depth_passes : 4;
+    // MSD path: the bucket sort also emits the super-tile entries (into geometry arrays of fixed
+    // capacity, so no host value is needed); used below when they fitted
+    const bool fused_emit = !depth_order_uses_pass_count(P);
+    LSR_TRY(launch_depth_order(P, guess, f.L, geom, counters, &hb->stall, stream, debug, fused_emit, 0, placed),
+            "depth order");
+    // the extra levels' features of the visible Gaussians (radii are the preprocess's): enqueued here,
+    // so it runs while the host waits for the counts
+    if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
+    hm.mark();
+    // the binning buffer from the last forward's size while the GPU works (the allocator callback
+    // is host work that would otherwise sit between the wait and the binning launches)
+    char* binning = nullptr;
+    size_t binning_have = 0;
+    if (hb->binning_hint && hb->hint_P == P && hb->hint_W == W && hb->hint_H == H) {
+        binning = static_cast<char*>(f.alloc(f.user, LSR_BUF_BINNING, hb->binning_hint));
+        binning_have = binning ? hb->binning_hint : 0;
+    }
+    hm.mark();
+    LSR_TRY(wait_counters(hb, seq, stream), "wait counters");
+    hm.mark();
+    uint32_t host_cnt[8];
+    for (int i = 0; i < 8; i++) host_cnt[i] = (uint32_t)hb->slot[i];
+    if (host_cnt[kCntError] && s->prefiltered)
+        return fail(LSR_ERR_PREFILTERED, "lsr_forward: prefiltered=True but a Gaussian is outside the frustum");
+    const int64_t R = host_cnt[kCntRendered];
+    *f.num_rendered = R;
+    if (a->out_num_entries) *a->out_num_entries = (int64_t)host_cnt[kCntSuper];
+    if (R > 0) {
+        // sort only the bits the visible keys span (key - min <= max - min)
+        const uint32_t span = host_cnt[kCntKeyMax] - host_cnt[kCntKeyMin];
+        int bits = 0;
+        while (bits < 32 && (span >> bits) != 0) bits++;
+        const int passes = bits <= 8 ? 1 : (bits + 7) / 8;
+        if (depth_order_uses_pass_count(P)) hb->depth_passes = passes;
+        if (depth_order_uses_pass_count(P) && passes > guess) {  // short guess: clear the scan status, sort again
+            LSR_TRY(zero_fill(geom + f.L.scan_regions, 4 * kDepthScans * f.L.scan_region_geom, stream),
+                    "clear scan status");
+            LSR_TRY(launch_depth_order(P, passes, f.L, geom, counters, &hb->stall, stream, debug), "depth order");
+        }
+    }
+
+    const bool emitted = fused_emit && (int64_t)host_cnt[kCntSuper] <= f.L.fused_cap;
+    if (fused_emit && !emitted) {  // entries beyond the fused capacity: the depth order again, unfused
+        LSR_TRY(zero_fill(geom + f.L.scan_regions, 4 * f.L.zero_words, stream), "clear scan status");
+        LSR_TRY(launch_depth_order(P, guess, f.L, geom, counters, &hb->stall, stream, debug, false), "depth order");
+    }
+    const Layout L = make_layout(P, W, H, R, (int64_t)host_cnt[kCntSuper]);
+    if (!binning || L.binning_bytes > binning_have) {
+        binning = static_cast<char*>(f.alloc(f.user, LSR_BUF_BINNING, L.binning_bytes));
+        if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
+    }
+    hb->hint_P = P;
+    hb->hint_W = W;
+    hb->hint_H = H;
+    hb->binning_hint = L.binning_bytes + L.binning_bytes / 8;  // 12.5 % headroom for the next view
+    LSR_TRY(launch_binning(P, R, L, geom, image, binning, &hb->stall, stream, debug, emitted, DevCount{nullptr, nullptr},
+                           placed),
+            "binning");
+    if (f.deferred) LSR_TRY(wait_and_fill_language(a, L, geom, stream), "fill language");
+    hm.mark();
+    const int32_t rc = render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
+    hm.mark();
+    return rc;
+}
+
 // lsr_forward, and with lv lsr_forward_levels (validated there: inference, one phase, no capacity
 // mode, no fused loss, no deferred feature) or lsr_levels_step_forward (capacity mode; all phases but
 // the geometry one).
 static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
-                            void* stream_ptr, int64_t* num_rendered, LevelsCall* lv);
+                            void* stream_ptr, int64_t* num_rendered, LevelsCall* lv)
+{
+    if (!s || !a || !alloc || !num_rendered) return fail(LSR_ERR_INVALID, "lsr_forward: null argument");
+    if (const int32_t rc = check_forward_args(s, a, lv)) return rc;
+    const int P = a->P, W = s->image_width, H = s->image_height;
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = s->debug != 0;
+    *num_rendered = 0;
+    if (P == 0) return forward_empty_scene(s, a, alloc, user, stream, debug, lv);
+
+    HostMarks hm;
+    hm.mark();
+    ForwardCall f{s, a, alloc, user, stream, debug, num_rendered, lv, make_layout(P, W, H, 0, 0)};
+    const Layout& L = f.L;
+    if (L.supers > 65536) return fail(LSR_ERR_INVALID, "lsr_forward: image larger than 65536 super-tiles");
+    hipError_t herr = hipSuccess;
+    f.hb = t_host.get(&herr);
+    if (!f.hb) return fail(LSR_ERR_HIP, "lsr_forward: pinned host block", herr);
+    char* geom = f.geom = static_cast<char*>(alloc(user, LSR_BUF_GEOM, L.geom_bytes));
+    f.image = static_cast<char*>(alloc(user, LSR_BUF_IMAGE, L.image_bytes));
+    if (!f.geom || !f.image) return fail(LSR_ERR_ALLOC, "lsr_forward: geometry/image buffer allocation failed");
+    if (lv) {
+        lv->lev = static_cast<float4*>(alloc(user, LSR_BUF_LEVELS, lsr_levels_bytes(P, lv->levels)));
+        if (!lv->lev) return fail(LSR_ERR_ALLOC, "lsr_forward_levels: level buffer allocation failed");
+    }
+    // no memset: k_publish_counters initialises every counter word before anything reads it
+    f.counters = reinterpret_cast<uint32_t*>(f.image + L.counters);
+    f.placed = !depth_order_uses_pass_count(P) && placed_emit(L, a->phase == LSR_PHASE_GEOMETRY, msd_digits(P));
+    f.deferred = (a->language_ready || a->phase != LSR_PHASE_ALL) && s->include_feature && a->language_feature;
+    if (a->phase == LSR_PHASE_COMPOSITE || a->phase == LSR_PHASE_COMPOSITE_FILLED) return forward_composite(f);
+
+    PreprocessParams pp = preprocess_params(s, a, L, geom, f.counters);
+    if (f.placed) {  // the bucket sort's count table
+        pp.zero2 = reinterpret_cast<uint32_t*>(geom + L.sup_status);
+        pp.zero2_words = (int)sup_words(msd_digits(P));
+    }
+    pp.lang_deferred = f.deferred ? 1 : 0;
+    // the bound form's geometry phase (a cache miss): b into the plane and the identity table by the
+    // preprocess, which needs the point list's address: the binning buffer is taken first
+    char* bound_binning = nullptr;
+    if (a->flags & LSR_BIND_FORWARD) {
+        const Layout Lc = make_layout(P, W, H, a->capacity_rendered, entry_capacity(a, L));
+        bound_binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, Lc.binning_bytes));
+        if (!bound_binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
+        pp.plane = reinterpret_cast<float4*>(geom + L.lang_plane);
+        pp.bind = reinterpret_cast<ViewBind*>(geom + L.view_bind);
+        pp.bind_point_list = reinterpret_cast<const uint32_t*>(bound_binning + Lc.point_list);
+    }
+    LSR_TRY(launch_preprocess(pp, stream), "preprocess");
+    hm.mark();
+    const uint32_t fwd_flags = forward_flags_word(a->flags, a->out_loss && s->include_feature && a->language_feature);
+    if (a->capacity_rendered > 0) return forward_capacity(f, pp.partial, fwd_flags, bound_binning);
+    return forward_eager(f, pp.partial, fwd_flags, hm);
+}
+
+// lsr_forward_levels and lsr_levels_step_forward (who) after their null check: the checks they share, in
+// the order both make them, and the forward.  The entry point's own checks (fwd.phase and the capacity
+// fields) sit between the shared ones: own(a) makes them, 0 when they pass.  reserved: a reserved field of
+// its args is set; flags_text: its wording of the fwd.flags refusal.
+template <class Own>
+static int32_t forward_levels(const char* who, const lsr_settings* s, const lsr_forward_levels_args* la, bool reserved,
+                              const char* flags_text, Own own, lsr_alloc_fn alloc, void* user, void* stream_ptr,
+                              int64_t* num_rendered)
+{
+    const lsr_forward_args* a = &la->fwd;
+    if (la->levels < 1 || la->levels > LSR_MAX_LEVELS) return invalid(who, "levels must be 1..LSR_MAX_LEVELS (4)");
+    if (reserved) return invalid(who, "reserved must be 0");
+    if (!s->include_feature) return invalid(who, "needs settings.include_feature");
+    if (a->flags != LSR_FWD_NO_BACKWARD) return invalid(who, flags_text);
+    if (a->loss_target) return invalid(who, "no fused loss, fwd.loss_target must be NULL");
+    if (a->loss_mask) return invalid(who, "no fused loss, fwd.loss_mask must be NULL");
+    if (a->out_loss) return invalid(who, "no fused loss, fwd.out_loss must be NULL");
+    if (a->language_ready) return invalid(who, "fwd.language_ready must be NULL");
+    if (const int32_t rc = own(a)) return rc;
+    if (a->P > 0 && !a->language_feature) return invalid(who, "fwd.language_feature (level 0) is NULL");
+    if (la->levels > 1 && a->P > 0 && !la->more_language_feature)
+        return invalid(who, "more_language_feature is NULL with levels > 1");
+    if (la->levels > 1 && !la->more_out_language_feature)
+        return invalid(who, "more_out_language_feature is NULL with levels > 1");
+    if (la->levels == 1) return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, nullptr);
+    LevelsCall lv{la->levels, la->more_language_feature, la->more_out_language_feature, nullptr};
+    return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, &lv);
+}
+
+// The checks of lsr_backward_levels and lsr_levels_step_backward (who; A: its args struct, whose fields
+// of these names mean the same).  The step form has a second reserved field, takes num_rendered as the
+// forward's capacity (never 0) and may leave dL_dlanguage_feature NULL with update.
+template <class A>
+static int32_t check_levels_backward(const char* who, const lsr_settings* s, const A* a)
+{
+    constexpr bool step = std::is_same<A, lsr_levels_step_backward_args>::value;
+    if (!s) return invalid(who, "settings is NULL");
+    if (!a) return invalid(who, "args is NULL");
+    if (a->levels < 1 || a->levels > LSR_MAX_LEVELS) return invalid(who, "levels must be 1..LSR_MAX_LEVELS (4)");
+    bool reserved = a->reserved != 0;
+    if constexpr (step) reserved = reserved || a->reserved2 != 0;
+    if (reserved) return invalid(who, "reserved must be 0");
+    if (a->P < 0) return invalid(who, "P must not be negative");
+    if (a->num_rendered < 0) return invalid(who, "num_rendered must not be negative");
+    if (!s->include_feature) return invalid(who, "needs settings.include_feature");
+    if (s->image_width <= 0 || s->image_height <= 0) return invalid(who, "invalid settings.image_width / image_height");
+    if (a->P > 0) {
+        if constexpr (step) {
+            if (a->num_rendered == 0) return invalid(who, "num_rendered is the forward's capacity, > 0");
+        }
+        if (!a->geom_buffer) return invalid(who, "geom_buffer is NULL");
+        if (!a->binning_buffer) return invalid(who, "binning_buffer is NULL");
+        if (!a->image_buffer) return invalid(who, "image_buffer is NULL");
+        if (!a->radii) return invalid(who, "radii is NULL");
+        if (!a->scratch) return invalid(who, "scratch is NULL");
+        if constexpr (step) {
+            if (!a->dL_dlanguage_feature && !a->update) return invalid(who, "dL_dlanguage_feature is NULL without update");
+        } else {
+            if (!a->dL_dlanguage_feature) return invalid(who, "dL_dlanguage_feature is NULL");
+        }
+        if ((a->raw & LSR_RAW_LANGUAGE) && !a->language_feature)
+            return invalid(who, "language_feature is NULL with raw & LSR_RAW_LANGUAGE");
+    }
+    const int fused = (a->out_language_feature ? 1 : 0) + (a->loss_target ? 1 : 0) + (a->loss_mask ? 1 : 0) +
+                      (a->dL_dloss ? 1 : 0);
+    if (fused != 0 && fused != 4)
+        return invalid(who, "the fused seed needs out_language_feature, loss_target, loss_mask and dL_dloss, all four "
+                            "or none");
+    if (fused == 0 && !a->dL_dout_language_feature)
+        return invalid(who, "no seed, give dL_dout_language_feature or the fused seed (dL_dloss)");
+    return LSR_OK;
+}
 
 extern "C" {
 
@@ -404,301 +848,11 @@ int32_t lsr_state_layout_of(int32_t P, int32_t width, int32_t height, int64_t nu
     return LSR_OK;
 }
 
-// The deferred language feature (lsr_forward_args.language_ready): the feature's update (another
-// stream) has overlapped everything enqueued so far; the stream waits for it, then the visible
-// Gaussians' records receive the feature.  Inside a graph capture the event is one recorded in the
-// same capture (a join of the two branches).
-static hipError_t wait_and_fill_language(const lsr_forward_args* a, const Layout& L, char* geom, hipStream_t stream)
-{
-    hipError_t e = hipStreamWaitEvent(stream, static_cast<hipEvent_t>(a->language_ready), 0);
-    if (e != hipSuccess) return e;
-    return launch_fill_language(a->P, a->language_feature, a->raw, a->radii, reinterpret_cast<float4*>(geom + L.record),
-                                stream);
-}
-
 int32_t lsr_forward(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
                     void* stream_ptr, int64_t* num_rendered)
 {
     return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, nullptr);
 }
-
-}  // extern "C"
-
-static int32_t forward_impl(const lsr_settings* s, const lsr_forward_args* a, lsr_alloc_fn alloc, void* user,
-                            void* stream_ptr, int64_t* num_rendered, LevelsCall* lv)
-{
-    if (!s || !a || !alloc || !num_rendered) return fail(LSR_ERR_INVALID, "lsr_forward: null argument");
-    const int P = a->P, W = s->image_width, H = s->image_height;
-    if (P < 0 || W <= 0 || H <= 0 || W > 65535 * kTile || H > 65535 * kTile)
-        return fail(LSR_ERR_INVALID, "lsr_forward: invalid P or image size");
-    if (s->sh_degree < 0 || s->sh_degree > 3) return fail(LSR_ERR_INVALID, "lsr_forward: sh_degree must be 0..3");
-    if (!a->out_color || !a->out_language_feature || (P > 0 && (!a->radii || !a->means3D || !a->opacities)))
-        return fail(LSR_ERR_INVALID, "lsr_forward: missing input/output pointer");
-    if (P > 0 && (!a->shs) == (!a->colors_precomp))
-        return fail(LSR_ERR_INVALID, "lsr_forward: provide exactly one of shs / colors_precomp");
-    if (P > 0 && ((a->scales && a->rotations) ? 1 : 0) == (a->cov3D_precomp ? 1 : 0))
-        return fail(LSR_ERR_INVALID, "lsr_forward: provide exactly one of scales+rotations / cov3D_precomp");
-    if (a->shs && (a->M < (s->sh_degree + 1) * (s->sh_degree + 1)))
-        return fail(LSR_ERR_INVALID, "lsr_forward: M smaller than (sh_degree+1)^2");
-    if (!s->bg || !s->viewmatrix || !s->projmatrix || !s->campos)
-        return fail(LSR_ERR_INVALID, "lsr_forward: settings tensors missing");
-    if (a->raw & ~(LSR_RAW_OPACITY | LSR_RAW_SCALES | LSR_RAW_ROTATIONS | LSR_RAW_LANGUAGE))
-        return fail(LSR_ERR_INVALID, "lsr_forward: unknown raw flag");
-    if (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD | LSR_BIND_FORWARD))
-        return fail(LSR_ERR_INVALID, "lsr_forward: unknown flag");
-    const bool bound = (a->flags & LSR_BIND_FORWARD) != 0;
-    if (bound && (a->phase == LSR_PHASE_ALL || lv))
-        return fail(LSR_ERR_INVALID, "lsr_forward: LSR_BIND_FORWARD needs a forward phase (capacity mode) of lsr_forward");
-    if (a->shs_rest && (!a->shs || a->M < 2))
-        return fail(LSR_ERR_INVALID, "lsr_forward: shs_rest needs shs (features_dc) and M >= 2");
-    if (a->capacity_rendered < 0 || (a->capacity_rendered > 0 && a->capacity_entries <= 0) ||
-        a->capacity_rendered > 0xFFFFFFFFll || a->capacity_entries > 0xFFFFFFFFll)
-        return fail(LSR_ERR_INVALID, "lsr_forward: capacity mode needs capacity_rendered > 0 and capacity_entries > 0 "
-                                     "(both < 2^32)");
-    if (a->phase < LSR_PHASE_ALL || a->phase > LSR_PHASE_COMPOSITE_FILLED ||
-        (a->phase != LSR_PHASE_ALL && (a->capacity_rendered <= 0 || a->language_ready)))
-        return fail(LSR_ERR_INVALID, "lsr_forward: a forward phase needs capacity mode and no language_ready");
-    if (a->out_num_entries) *a->out_num_entries = 0;
-    if (a->out_loss && (!s->include_feature || (P > 0 && !a->language_feature) || !a->loss_target || !a->loss_mask))
-        return fail(LSR_ERR_INVALID, "lsr_forward: the fused loss needs include_feature, language_feature, "
-                                     "loss_target and loss_mask");
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
-    const bool debug = s->debug != 0;
-    *num_rendered = 0;
-    const size_t HW = (size_t)W * H;
-    if (P == 0) {
-        // upstream leaves the images at their zero initialisation when there is nothing to draw
-        LSR_TRY(zero_fill(a->out_color, 3 * HW * 4, stream), "memset color");
-        LSR_TRY(zero_fill(a->out_language_feature, 3 * HW * 4, stream), "memset language");
-        if (lv) LSR_TRY(zero_fill(lv->out_more, (size_t)(lv->levels - 1) * 3 * HW * 4, stream), "memset language");
-        if (a->out_loss) {
-            const Layout L0 = make_layout(0, W, H, 0, 0);
-            char* image = static_cast<char*>(alloc(user, LSR_BUF_IMAGE, L0.image_bytes));
-            if (!image) return fail(LSR_ERR_ALLOC, "lsr_forward: image buffer allocation failed");
-            RenderParams rp{};
-            rp.W = W;
-            rp.H = H;
-            rp.loss_gt = a->loss_target;
-            rp.loss_mask = a->loss_mask;
-            rp.loss_code = reinterpret_cast<uint8_t*>(image + L0.loss_code);
-            rp.loss_partial = reinterpret_cast<double*>(image + L0.loss_partial);
-            rp.out_loss = a->out_loss;
-            LSR_TRY(launch_loss_background(rp, stream), "loss");
-        }
-        return LSR_OK;
-    }
-
-    HostMarks hm;
-    hm.mark();
-    Layout L = make_layout(P, W, H, 0, 0);
-    if (L.supers > 65536) return fail(LSR_ERR_INVALID, "lsr_forward: image larger than 65536 super-tiles");
-    hipError_t herr = hipSuccess;
-    HostBlock* hb = t_host.get(&herr);
-    if (!hb) return fail(LSR_ERR_HIP, "lsr_forward: pinned host block", herr);
-    char* geom = static_cast<char*>(alloc(user, LSR_BUF_GEOM, L.geom_bytes));
-    char* image = static_cast<char*>(alloc(user, LSR_BUF_IMAGE, L.image_bytes));
-    if (!geom || !image) return fail(LSR_ERR_ALLOC, "lsr_forward: geometry/image buffer allocation failed");
-    if (lv) {
-        lv->lev = static_cast<float4*>(alloc(user, LSR_BUF_LEVELS, lsr_levels_bytes(P, lv->levels)));
-        if (!lv->lev) return fail(LSR_ERR_ALLOC, "lsr_forward_levels: level buffer allocation failed");
-    }
-    // no memset: k_publish_counters initialises every counter word before anything reads it
-    uint32_t* counters = reinterpret_cast<uint32_t*>(image + L.counters);
-
-    PreprocessParams pp{};
-    pp.P = P;
-    pp.M = a->M;
-    pp.D = s->sh_degree;
-    pp.W = W;
-    pp.H = H;
-    pp.gx = L.gx;
-    pp.gy = L.gy;
-    pp.tanfovx = s->tanfovx;
-    pp.tanfovy = s->tanfovy;
-    pp.focal_y = (float)H / (2.0f * s->tanfovy);
-    pp.focal_x = (float)W / (2.0f * s->tanfovx);
-    pp.scale_modifier = s->scale_modifier;
-    pp.include_feature = s->include_feature;
-    pp.prefiltered = s->prefiltered;
-    pp.means = a->means3D;
-    pp.shs = a->shs;
-    pp.colors = a->colors_precomp;
-    pp.lang = a->language_feature;
-    pp.opac = a->opacities;
-    pp.scales = a->scales;
-    pp.rots = a->rotations;
-    pp.cov_pre = a->cov3D_precomp;
-    pp.view = s->viewmatrix;
-    pp.proj = s->projmatrix;
-    pp.campos = s->campos;
-    pp.radii = a->radii;
-    pp.visible = a->visible;
-    pp.depth_key = reinterpret_cast<uint32_t*>(geom + L.depth_key);
-    pp.tiles = reinterpret_cast<uint32_t*>(geom + L.tiles_touched);
-    pp.rect = reinterpret_cast<uint32_t*>(geom + L.rect);
-    pp.clamped = reinterpret_cast<uint32_t*>(geom + L.clamped);
-    pp.record = reinterpret_cast<float4*>(geom + L.record);
-    pp.counters = counters;
-    pp.zero = reinterpret_cast<uint32_t*>(geom + L.scan_regions);
-    pp.zero_words = (int)L.zero_words;  // depth-sort scan status and the fused loss's words
-    // placed emission (the MSD depth order's fused emission at super-tile-major positions)
-    const bool placed = !depth_order_uses_pass_count(P) && placed_emit(L, a->phase == LSR_PHASE_GEOMETRY, msd_digits(P));
-    if (placed) {  // the bucket sort's count table
-        pp.zero2 = reinterpret_cast<uint32_t*>(geom + L.sup_status);
-        pp.zero2_words = (int)sup_words(msd_digits(P));
-    }
-    pp.raw = a->raw;
-    pp.shs_rest = a->shs_rest;
-    pp.partial = reinterpret_cast<uint4*>(geom + L.pre_partial);
-    // deferred language feature: geometry first, the feature after the caller's event (or, split in
-    // phases, in the composite call)
-    const bool deferred = (a->language_ready || a->phase != LSR_PHASE_ALL) && s->include_feature && a->language_feature;
-    pp.lang_deferred = deferred ? 1 : 0;
-    if (a->phase == LSR_PHASE_COMPOSITE || a->phase == LSR_PHASE_COMPOSITE_FILLED) {
-        // the geometry call's buffers (same allocator keys and sizes): the feature (unless a fused
-        // update already wrote it, LSR_PHASE_COMPOSITE_FILLED), then the compositing
-        const int64_t R_cap = a->capacity_rendered;
-        const int64_t E_cap = !depth_order_uses_pass_count(P) ? std::min<int64_t>(a->capacity_entries, L.fused_cap)
-                                                                : a->capacity_entries;
-        L = make_layout(P, W, H, R_cap, E_cap);
-        char* binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, L.binning_bytes));
-        if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
-        *num_rendered = R_cap;
-        if (deferred && a->phase == LSR_PHASE_COMPOSITE) {
-            LSR_TRY(launch_fill_language(P, a->language_feature, a->raw, a->radii,
-                                         reinterpret_cast<float4*>(geom + (bound ? L.lang_plane : L.record)), stream,
-                                         bound ? 1 : 0),
-                    "fill language");
-            if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
-        }
-        return render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
-    }
-    // the bound form's geometry phase (a cache miss): b into the plane and the identity table by the
-    // preprocess, which needs the point list's address: the binning buffer is taken first
-    char* bound_binning = nullptr;
-    if (bound) {
-        const int64_t E_cap = !depth_order_uses_pass_count(P) ? std::min<int64_t>(a->capacity_entries, L.fused_cap)
-                                                                : a->capacity_entries;
-        const Layout Lc = make_layout(P, W, H, a->capacity_rendered, E_cap);
-        bound_binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, Lc.binning_bytes));
-        if (!bound_binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
-        pp.plane = reinterpret_cast<float4*>(geom + L.lang_plane);
-        pp.bind = reinterpret_cast<ViewBind*>(geom + L.view_bind);
-        pp.bind_point_list = reinterpret_cast<const uint32_t*>(bound_binning + Lc.point_list);
-    }
-    LSR_TRY(launch_preprocess(pp, stream), "preprocess");
-    hm.mark();
-
-    // The one host wait: num_rendered R and the super-tile entries E size the binning buffer, and
-    // the visible depth-key range fixes the number of depth-sort passes.  The depth sort is enqueued
-    // BEFORE the wait, with this thread's last pass count: it reads the key range on the device, and
-    // any pass count >= the needed one gives the same order (the extra digits are all 0), so the GPU
-    // sorts while the host waits, instead of idling until the host has enqueued the next launch.
-    // Should the range need more passes than guessed, the sort is run again below.
-    const uint32_t fwd_flags = ((a->flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) |
-                               ((a->out_loss && s->include_feature && a->language_feature) ? kFwdFusedLoss : 0u) |
-                               ((a->flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) |
-                               ((a->flags & LSR_FWD_NO_BACKWARD) ? kFwdNoBackward : 0u);
-    if (a->capacity_rendered > 0) {
-        // Capacity mode: nothing waits for the device.  The counters stay on the device, the binning's
-        // grids and buffers come from the capacities and its kernels read the true counts; a view over
-        // capacity sets counters[kCntOverflow] (and *overflow) and is not binned.
-        const int64_t R_cap = a->capacity_rendered;
-        const bool fused = !depth_order_uses_pass_count(P);
-        const int64_t E_cap = fused ? std::min<int64_t>(a->capacity_entries, L.fused_cap) : a->capacity_entries;
-        // LSD order (large P): the passes this thread's last eager forward needed (its key range is
-        // not read on the host here; a view that needs more is flagged as over capacity)
-        const int passes = fused ? 0 : (hb->depth_passes > 0 ? hb->depth_passes : 4);
-        LSR_TRY(launch_publish_counters((P + kPreThreads - 1) / kPreThreads, pp.partial, counters, nullptr, 0,
-                                        fwd_flags, (uint32_t)R_cap, (uint32_t)E_cap, a->overflow, passes, stream),
-                "publish counters");
-        LSR_TRY(launch_depth_order(P, fused ? 4 : passes, L, geom, counters, &hb->stall, stream, debug, fused,
-                                   (uint32_t)E_cap, placed),
-                "depth order");
-        L = make_layout(P, W, H, R_cap, E_cap);
-        char* binning = bound_binning ? bound_binning : static_cast<char*>(alloc(user, LSR_BUF_BINNING, L.binning_bytes));
-        if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
-        LSR_TRY(launch_binning(P, R_cap, L, geom, image, binning, &hb->stall, stream, debug, fused,
-                               DevCount{counters + kCntSuper, counters + kCntOverflow}, placed),
-                "binning");
-        *num_rendered = R_cap;
-        if (a->phase == LSR_PHASE_GEOMETRY) return LSR_OK;
-        if (deferred) LSR_TRY(wait_and_fill_language(a, L, geom, stream), "fill language");
-        // (lsr_levels_step_forward, one phase: level 0 went into the records in the preprocess)
-        if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
-        return render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
-    }
-    const uint32_t seq = ++hb->seq == 0 ? ++hb->seq : hb->seq;
-    LSR_TRY(launch_publish_counters((P + kPreThreads - 1) / kPreThreads, pp.partial, counters, hb->slot, seq,
-                                    fwd_flags, 0u, 0u, nullptr, 0, stream),
-            "publish counters");
-    const int guess = hb->depth_passes > 0 ? hb->depth_passes : 4;
-    // MSD path: the bucket sort also emits the super-tile entries (into geometry arrays of fixed
-    // capacity, so no host value is needed); used below when they fitted
-    const bool fused_emit = !depth_order_uses_pass_count(P);
-    LSR_TRY(launch_depth_order(P, guess, L, geom, counters, &hb->stall, stream, debug, fused_emit, 0, placed),
-            "depth order");
-    // the extra levels' features of the visible Gaussians (radii are the preprocess's): enqueued here,
-    // so it runs while the host waits for the counts
-    if (lv) LSR_TRY(launch_fill_levels(P, lv->levels, lv->more, a->raw, a->radii, lv->lev, stream), "fill levels");
-    hm.mark();
-    // the binning buffer from the last forward's size while the GPU works (the allocator callback
-    // is host work that would otherwise sit between the wait and the binning launches)
-    char* binning = nullptr;
-    size_t binning_have = 0;
-    if (hb->binning_hint && hb->hint_P == P && hb->hint_W == W && hb->hint_H == H) {
-        binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, hb->binning_hint));
-        binning_have = binning ? hb->binning_hint : 0;
-    }
-    hm.mark();
-    LSR_TRY(wait_counters(hb, seq, stream), "wait counters");
-    hm.mark();
-    uint32_t host_cnt[8];
-    for (int i = 0; i < 8; i++) host_cnt[i] = (uint32_t)hb->slot[i];
-    if (host_cnt[kCntError] && s->prefiltered)
-        return fail(LSR_ERR_PREFILTERED, "lsr_forward: prefiltered=True but a Gaussian is outside the frustum");
-    const int64_t R = host_cnt[kCntRendered];
-    *num_rendered = R;
-    if (a->out_num_entries) *a->out_num_entries = (int64_t)host_cnt[kCntSuper];
-    if (R > 0) {
-        // sort only the bits the visible keys span (key - min <= max - min)
-        const uint32_t span = host_cnt[kCntKeyMax] - host_cnt[kCntKeyMin];
-        int bits = 0;
-        while (bits < 32 && (span >> bits) != 0) bits++;
-        const int passes = bits <= 8 ? 1 : (bits + 7) / 8;
-        if (depth_order_uses_pass_count(P)) hb->depth_passes = passes;
-        if (depth_order_uses_pass_count(P) && passes > guess) {  // short guess: clear the scan status, sort again
-            LSR_TRY(zero_fill(geom + L.scan_regions, 4 * kDepthScans * L.scan_region_geom, stream),
-                    "clear scan status");
-            LSR_TRY(launch_depth_order(P, passes, L, geom, counters, &hb->stall, stream, debug), "depth order");
-        }
-    }
-
-    const bool emitted = fused_emit && (int64_t)host_cnt[kCntSuper] <= L.fused_cap;
-    if (fused_emit && !emitted) {  // entries beyond the fused capacity: the depth order again, unfused
-        LSR_TRY(zero_fill(geom + L.scan_regions, 4 * L.zero_words, stream), "clear scan status");
-        LSR_TRY(launch_depth_order(P, guess, L, geom, counters, &hb->stall, stream, debug, false), "depth order");
-    }
-    L = make_layout(P, W, H, R, (int64_t)host_cnt[kCntSuper]);
-    if (!binning || L.binning_bytes > binning_have) {
-        binning = static_cast<char*>(alloc(user, LSR_BUF_BINNING, L.binning_bytes));
-        if (!binning) return fail(LSR_ERR_ALLOC, "lsr_forward: binning buffer allocation failed");
-    }
-    hb->hint_P = P;
-    hb->hint_W = W;
-    hb->hint_H = H;
-    hb->binning_hint = L.binning_bytes + L.binning_bytes / 8;  // 12.5 % headroom for the next view
-    LSR_TRY(launch_binning(P, R, L, geom, image, binning, &hb->stall, stream, debug, emitted, DevCount{nullptr, nullptr},
-                           placed),
-            "binning");
-    if (deferred) LSR_TRY(wait_and_fill_language(a, L, geom, stream), "fill language");
-    hm.mark();
-    const int32_t rc = render_forward_and_finish(s, a, L, geom, image, binning, hb, stream, debug, lv);
-    hm.mark();
-    return rc;
-}
-
-extern "C" {
 
 int32_t lsr_debug_levels_occupancy(int32_t levels)
 {
@@ -717,30 +871,15 @@ size_t lsr_levels_bytes(int32_t P, int32_t levels)
 int32_t lsr_forward_levels(const lsr_settings* s, const lsr_forward_levels_args* la, lsr_alloc_fn alloc, void* user,
                            void* stream_ptr, int64_t* num_rendered)
 {
-    if (!s || !la || !alloc || !num_rendered) return fail(LSR_ERR_INVALID, "lsr_forward_levels: null argument");
-    const lsr_forward_args* a = &la->fwd;
-    if (la->levels < 1 || la->levels > LSR_MAX_LEVELS)
-        return fail(LSR_ERR_INVALID, "lsr_forward_levels: levels must be 1..LSR_MAX_LEVELS (4)");
-    if (la->reserved != 0) return fail(LSR_ERR_INVALID, "lsr_forward_levels: reserved must be 0");
-    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_forward_levels: needs settings.include_feature");
-    if (a->flags != LSR_FWD_NO_BACKWARD)
-        return fail(LSR_ERR_INVALID, "lsr_forward_levels: inference only, fwd.flags must be LSR_FWD_NO_BACKWARD");
-    if (a->loss_target) return fail(LSR_ERR_INVALID, "lsr_forward_levels: no fused loss, fwd.loss_target must be NULL");
-    if (a->loss_mask) return fail(LSR_ERR_INVALID, "lsr_forward_levels: no fused loss, fwd.loss_mask must be NULL");
-    if (a->out_loss) return fail(LSR_ERR_INVALID, "lsr_forward_levels: no fused loss, fwd.out_loss must be NULL");
-    if (a->language_ready) return fail(LSR_ERR_INVALID, "lsr_forward_levels: fwd.language_ready must be NULL");
-    if (a->phase != LSR_PHASE_ALL) return fail(LSR_ERR_INVALID, "lsr_forward_levels: fwd.phase must be LSR_PHASE_ALL");
-    if (a->capacity_rendered != 0)
-        return fail(LSR_ERR_INVALID, "lsr_forward_levels: no capacity mode, fwd.capacity_rendered must be 0");
-    if (a->P > 0 && !a->language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_forward_levels: fwd.language_feature (level 0) is NULL");
-    if (la->levels > 1 && a->P > 0 && !la->more_language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_forward_levels: more_language_feature is NULL with levels > 1");
-    if (la->levels > 1 && !la->more_out_language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_forward_levels: more_out_language_feature is NULL with levels > 1");
-    if (la->levels == 1) return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, nullptr);
-    LevelsCall lv{la->levels, la->more_language_feature, la->more_out_language_feature, nullptr};
-    return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, &lv);
+    static const char who[] = "lsr_forward_levels";
+    if (!s || !la || !alloc || !num_rendered) return invalid(who, "null argument");
+    const auto own = [](const lsr_forward_args* a) {
+        if (a->phase != LSR_PHASE_ALL) return invalid(who, "fwd.phase must be LSR_PHASE_ALL");
+        if (a->capacity_rendered != 0) return invalid(who, "no capacity mode, fwd.capacity_rendered must be 0");
+        return (int32_t)LSR_OK;
+    };
+    return forward_levels(who, s, la, la->reserved != 0, "inference only, fwd.flags must be LSR_FWD_NO_BACKWARD", own,
+                          alloc, user, stream_ptr, num_rendered);
 }
 
 size_t lsr_backward_levels_bytes(int32_t P, int32_t levels)
@@ -751,34 +890,8 @@ size_t lsr_backward_levels_bytes(int32_t P, int32_t levels)
 
 int32_t lsr_backward_levels(const lsr_settings* s, const lsr_backward_levels_args* a, void* stream_ptr)
 {
-    if (!s) return fail(LSR_ERR_INVALID, "lsr_backward_levels: settings is NULL");
-    if (!a) return fail(LSR_ERR_INVALID, "lsr_backward_levels: args is NULL");
-    if (a->levels < 1 || a->levels > LSR_MAX_LEVELS)
-        return fail(LSR_ERR_INVALID, "lsr_backward_levels: levels must be 1..LSR_MAX_LEVELS (4)");
-    if (a->reserved != 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: reserved must be 0");
-    if (a->P < 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: P must not be negative");
-    if (a->num_rendered < 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: num_rendered must not be negative");
-    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_backward_levels: needs settings.include_feature");
-    const int P = a->P, W = s->image_width, H = s->image_height, levels = a->levels;
-    if (W <= 0 || H <= 0) return fail(LSR_ERR_INVALID, "lsr_backward_levels: invalid settings.image_width / image_height");
-    if (P > 0) {
-        if (!a->geom_buffer) return fail(LSR_ERR_INVALID, "lsr_backward_levels: geom_buffer is NULL");
-        if (!a->binning_buffer) return fail(LSR_ERR_INVALID, "lsr_backward_levels: binning_buffer is NULL");
-        if (!a->image_buffer) return fail(LSR_ERR_INVALID, "lsr_backward_levels: image_buffer is NULL");
-        if (!a->radii) return fail(LSR_ERR_INVALID, "lsr_backward_levels: radii is NULL");
-        if (!a->scratch) return fail(LSR_ERR_INVALID, "lsr_backward_levels: scratch is NULL");
-        if (!a->dL_dlanguage_feature) return fail(LSR_ERR_INVALID, "lsr_backward_levels: dL_dlanguage_feature is NULL");
-        if ((a->raw & LSR_RAW_LANGUAGE) && !a->language_feature)
-            return fail(LSR_ERR_INVALID, "lsr_backward_levels: language_feature is NULL with raw & LSR_RAW_LANGUAGE");
-    }
-    const int fused = (a->out_language_feature ? 1 : 0) + (a->loss_target ? 1 : 0) + (a->loss_mask ? 1 : 0) +
-                      (a->dL_dloss ? 1 : 0);
-    if (fused != 0 && fused != 4)
-        return fail(LSR_ERR_INVALID, "lsr_backward_levels: the fused seed needs out_language_feature, loss_target, "
-                                     "loss_mask and dL_dloss, all four or none");
-    if (fused == 0 && !a->dL_dout_language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_backward_levels: no seed, give dL_dout_language_feature or the fused seed "
-                                     "(dL_dloss)");
+    if (const int32_t rc = check_levels_backward("lsr_backward_levels", s, a)) return rc;
+    const int P = a->P, levels = a->levels;
     if (P == 0) return LSR_OK;
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
     const bool debug = s->debug != 0;
@@ -787,91 +900,35 @@ int32_t lsr_backward_levels(const lsr_settings* s, const lsr_backward_levels_arg
                 "memset dlang levels");
         return LSR_OK;
     }
-    if (const int32_t rc = levels_grad_walk(s, a, stream, debug)) return rc;
-    LSR_TRY(launch_levels_grad_epilogue(P, levels, a->radii, static_cast<float*>(a->scratch),
-                                        (a->raw & LSR_RAW_LANGUAGE) ? a->language_feature : nullptr,
-                                        a->dL_dlanguage_feature, stream),
-            "levels grad epilogue");
-    return LSR_OK;
+    return levels_grad_walk(s, a, stream, debug, true);
 }
 
 int32_t lsr_levels_step_forward(const lsr_settings* s, const lsr_levels_step_forward_args* sa, lsr_alloc_fn alloc,
                                 void* user, void* stream_ptr, int64_t* num_rendered)
 {
-    if (!s || !sa || !alloc || !num_rendered) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: null argument");
+    static const char who[] = "lsr_levels_step_forward";
+    if (!s || !sa || !alloc || !num_rendered) return invalid(who, "null argument");
     const lsr_forward_levels_args* la = &sa->levels;
-    const lsr_forward_args* a = &la->fwd;
-    if (la->levels < 1 || la->levels > LSR_MAX_LEVELS)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: levels must be 1..LSR_MAX_LEVELS (4)");
-    if (sa->reserved != 0 || la->reserved != 0)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: reserved must be 0");
-    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: needs settings.include_feature");
-    if (a->flags != LSR_FWD_NO_BACKWARD)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.flags must be LSR_FWD_NO_BACKWARD (the gradient walk "
-                                     "needs no backward state)");
-    if (a->loss_target)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: no fused loss, fwd.loss_target must be NULL");
-    if (a->loss_mask) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: no fused loss, fwd.loss_mask must be NULL");
-    if (a->out_loss) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: no fused loss, fwd.out_loss must be NULL");
-    if (a->language_ready) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.language_ready must be NULL");
-    if (a->capacity_rendered <= 0)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: capacity mode only, fwd.capacity_rendered must be > 0");
-    if (a->capacity_entries <= 0)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: capacity mode only, fwd.capacity_entries must be > 0");
-    if (!a->overflow) return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: capacity mode only, fwd.overflow is NULL");
-    if (a->phase == LSR_PHASE_GEOMETRY)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.phase LSR_PHASE_GEOMETRY is lsr_forward's (the "
-                                     "geometry does not depend on the levels): call lsr_forward with that phase");
-    if (a->phase != LSR_PHASE_ALL && a->phase != LSR_PHASE_COMPOSITE && a->phase != LSR_PHASE_COMPOSITE_FILLED)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.phase must be LSR_PHASE_ALL, LSR_PHASE_COMPOSITE or "
-                                     "LSR_PHASE_COMPOSITE_FILLED");
-    if (a->P > 0 && !a->language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: fwd.language_feature (level 0) is NULL");
-    if (la->levels > 1 && a->P > 0 && !la->more_language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: more_language_feature is NULL with levels > 1");
-    if (la->levels > 1 && !la->more_out_language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_forward: more_out_language_feature is NULL with levels > 1");
-    if (la->levels == 1) return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, nullptr);
-    LevelsCall lv{la->levels, la->more_language_feature, la->more_out_language_feature, nullptr};
-    return forward_impl(s, a, alloc, user, stream_ptr, num_rendered, &lv);
+    const auto own = [](const lsr_forward_args* a) {
+        if (a->capacity_rendered <= 0) return invalid(who, "capacity mode only, fwd.capacity_rendered must be > 0");
+        if (a->capacity_entries <= 0) return invalid(who, "capacity mode only, fwd.capacity_entries must be > 0");
+        if (!a->overflow) return invalid(who, "capacity mode only, fwd.overflow is NULL");
+        if (a->phase == LSR_PHASE_GEOMETRY)
+            return invalid(who, "fwd.phase LSR_PHASE_GEOMETRY is lsr_forward's (the geometry does not depend on the "
+                                "levels): call lsr_forward with that phase");
+        if (a->phase != LSR_PHASE_ALL && a->phase != LSR_PHASE_COMPOSITE && a->phase != LSR_PHASE_COMPOSITE_FILLED)
+            return invalid(who, "fwd.phase must be LSR_PHASE_ALL, LSR_PHASE_COMPOSITE or LSR_PHASE_COMPOSITE_FILLED");
+        return (int32_t)LSR_OK;
+    };
+    return forward_levels(who, s, la, sa->reserved != 0 || la->reserved != 0,
+                          "fwd.flags must be LSR_FWD_NO_BACKWARD (the gradient walk needs no backward state)", own, alloc,
+                          user, stream_ptr, num_rendered);
 }
 
 int32_t lsr_levels_step_backward(const lsr_settings* s, const lsr_levels_step_backward_args* a, void* stream_ptr)
 {
-    if (!s) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: settings is NULL");
-    if (!a) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: args is NULL");
-    if (a->levels < 1 || a->levels > LSR_MAX_LEVELS)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: levels must be 1..LSR_MAX_LEVELS (4)");
-    if (a->reserved != 0 || a->reserved2 != 0)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: reserved must be 0");
-    if (a->P < 0) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: P must not be negative");
-    if (a->num_rendered < 0)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: num_rendered must not be negative");
-    if (!s->include_feature) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: needs settings.include_feature");
-    const int P = a->P, W = s->image_width, H = s->image_height, levels = a->levels;
-    if (W <= 0 || H <= 0)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: invalid settings.image_width / image_height");
-    if (P > 0) {
-        if (a->num_rendered == 0)
-            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: num_rendered is the forward's capacity, > 0");
-        if (!a->geom_buffer) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: geom_buffer is NULL");
-        if (!a->binning_buffer) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: binning_buffer is NULL");
-        if (!a->image_buffer) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: image_buffer is NULL");
-        if (!a->radii) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: radii is NULL");
-        if (!a->scratch) return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: scratch is NULL");
-        if (!a->dL_dlanguage_feature && !a->update)
-            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: dL_dlanguage_feature is NULL without update");
-        if ((a->raw & LSR_RAW_LANGUAGE) && !a->language_feature)
-            return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: language_feature is NULL with raw & LSR_RAW_LANGUAGE");
-    }
-    const int fused = (a->out_language_feature ? 1 : 0) + (a->loss_target ? 1 : 0) + (a->loss_mask ? 1 : 0) +
-                      (a->dL_dloss ? 1 : 0);
-    if (fused != 0 && fused != 4)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: the fused seed needs out_language_feature, loss_target, "
-                                     "loss_mask and dL_dloss, all four or none");
-    if (fused == 0 && !a->dL_dout_language_feature)
-        return fail(LSR_ERR_INVALID, "lsr_levels_step_backward: no seed, give dL_dout_language_feature or the fused "
-                                     "seed (dL_dloss)");
+    if (const int32_t rc = check_levels_backward("lsr_levels_step_backward", s, a)) return rc;
+    const int P = a->P, levels = a->levels;
     if (a->update) {
         const lsr_adam_tensor& u = *a->update;
         if (!(a->raw & LSR_RAW_LANGUAGE))
@@ -897,19 +954,11 @@ int32_t lsr_levels_step_backward(const lsr_settings* s, const lsr_levels_step_ba
     const bool debug = s->debug != 0;
     // no early return for an empty view: num_rendered is the capacity.  A view that drew nothing, or
     // one over capacity, left empty ranges and no scheduled tile: the walk's workgroups all return
-    if (const int32_t rc = levels_grad_walk(s, a, stream, debug)) return rc;
-    float* acc = static_cast<float*>(a->scratch);
-    if (!a->update) {
-        LSR_TRY(launch_levels_grad_epilogue(P, levels, a->radii, acc,
-                                            (a->raw & LSR_RAW_LANGUAGE) ? a->language_feature : nullptr,
-                                            a->dL_dlanguage_feature, stream),
-                "levels grad epilogue");
-        return LSR_OK;
-    }
+    if (const int32_t rc = levels_grad_walk(s, a, stream, debug, !a->update)) return rc;
+    if (!a->update) return LSR_OK;
     const lsr_adam_tensor& u = *a->update;
-    AdamHyper h{u.lr, u.beta1, u.beta2, u.eps, u.step};
-    LSR_TRY(launch_levels_tail(P, levels, a->radii, acc, u.param, u.exp_avg, u.exp_avg_sq, a->dL_dlanguage_feature, h,
-                               a->update_step_dev, a->update_skip, reinterpret_cast<float4*>(a->fill_record),
+    LSR_TRY(launch_levels_tail(P, levels, a->radii, static_cast<float*>(a->scratch), u.param, u.exp_avg, u.exp_avg_sq, a->dL_dlanguage_feature,
+                               adam_hyper(u), a->update_step_dev, a->update_skip, reinterpret_cast<float4*>(a->fill_record),
                                static_cast<float4*>(a->fill_levels), stream),
             "levels tail");
     return LSR_OK;
@@ -998,24 +1047,10 @@ int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_allo
         LSR_TRY(zero_fill(grad, 4 * (size_t)stride * (size_t)P, stream), "memset grad");
     }
 
-    RenderParams rp{};
-    rp.W = W;
-    rp.H = H;
-    rp.gx = L.gx;
-    rp.gy = L.gy;
+    RenderParams rp = walk_params(W, H, L, geom, image, binning);
     rp.include_feature = (s->include_feature && a->language_feature) ? 1 : 0;
-    rp.ranges = reinterpret_cast<const uint2*>(image + L.ranges);
-    rp.point_list = reinterpret_cast<const uint32_t*>(binning + L.point_list);
-    rp.cover = reinterpret_cast<uint8_t*>(binning + L.cover);
-    rp.record = reinterpret_cast<const float4*>(geom + L.record);
     if (a->flags & LSR_BIND_BACKWARD) rp.bind = reinterpret_cast<const ViewBind*>(geom + L.view_bind);
     rp.bg = s->bg;
-    rp.final_T = reinterpret_cast<float*>(image + L.final_T);
-    rp.n_contrib = reinterpret_cast<uint32_t*>(image + L.n_contrib);
-    rp.sched_counts = reinterpret_cast<uint32_t*>(image + L.counters);
-    rp.sched_lists = reinterpret_cast<uint32_t*>(image + L.tile_lists);
-    rp.split_pool = reinterpret_cast<float*>(image + L.split_pool);
-    rp.split_desc = reinterpret_cast<uint4*>(image + L.split_desc);
     rp.dL_dcolor = a->dL_dout_color;
     rp.dL_dlang = a->dL_dout_language_feature;
     rp.dL_dloss = a->dL_dloss;
@@ -1041,9 +1076,9 @@ int32_t lsr_backward(const lsr_settings* s, const lsr_backward_args* a, lsr_allo
         if (defer) return LSR_OK;  // lsr_language_tail runs the rest after the caller's all-reduce
         // the language step's tail in one pass: epilogue + Adam (+ the next forward's feature slots)
         const lsr_adam_tensor& u = *a->update;
-        AdamHyper h{u.lr, u.beta1, u.beta2, u.eps, u.step};
         LSR_TRY(launch_language_tail(P, a->radii, grad, const_cast<float*>(a->language_feature), u.exp_avg, u.exp_avg_sq,
-                                     a->dL_dmeans2D, a->dL_dlanguage_feature, h, a->update_step_dev, a->update_skip,
+                                     a->dL_dmeans2D, a->dL_dlanguage_feature, adam_hyper(u), a->update_step_dev,
+                                     a->update_skip,
                                      reinterpret_cast<float4*>(a->fill_record), 0, stream,
                                      (a->flags & LSR_BIND_FILL_PLANE) ? 1 : 0),
                 "language tail");
@@ -1154,50 +1189,63 @@ int32_t lsr_view_counts(int32_t width, int32_t height, const void* image, uint32
     return LSR_OK;
 }
 
-static int32_t view_copy(const lsr_view_args* a, void* stream_ptr, bool restore)
+// The checks of a view call's args (a not null) that lsr_view_save / lsr_view_restore and lsr_view_bind
+// share, in each one's order; null when they pass.  pack_optional (lsr_view_bind): no pack is a miss, and
+// num_rendered and pack_bytes are then not looked at; a null buffer (null_buffer_text) answers before
+// num_rendered there, after it in the copies.
+static const char* view_args_error(const lsr_view_args* a, bool pack_optional, const char* null_buffer_text)
 {
-    const char* who = restore ? "lsr_view_restore" : "lsr_view_save";
-    char msg[160];
-    auto bad = [&](const char* what) {
-        snprintf(msg, sizeof(msg), "%s: %s", who, what);
-        return fail(LSR_ERR_INVALID, msg);
-    };
-    if (!a) return bad("null argument");
     if (a->P < 1 || a->width < 1 || a->height < 1 || a->width > 65535 * kTile || a->height > 65535 * kTile)
-        return bad("P, width and height must be positive");
+        return "P, width and height must be positive";
     if (a->capacity_rendered < 1 || a->capacity_entries < 1 || a->capacity_rendered > 0xFFFFFFFFll ||
         a->capacity_entries > 0xFFFFFFFFll)
-        return bad("the capacities must be positive (both < 2^32)");
-    if (a->num_rendered < 0 || a->num_rendered > a->capacity_rendered)
-        return bad("num_rendered must be 0 .. capacity_rendered");
-    if (!a->geom || !a->image || !a->binning || !a->radii || !a->pack) return bad("null buffer");
-    if (a->pack_bytes < lsr_view_pack_bytes(a->P, a->width, a->height, a->num_rendered))
-        return bad("pack_bytes is below lsr_view_pack_bytes");
+        return "the capacities must be positive (both < 2^32)";
+    const bool buffers = a->geom && a->image && a->binning && a->radii && (pack_optional || a->pack);
+    if (pack_optional && !buffers) return null_buffer_text;
+    if (a->pack || !pack_optional) {
+        if (a->num_rendered < 0 || a->num_rendered > a->capacity_rendered)
+            return "num_rendered must be 0 .. capacity_rendered";
+        if (!buffers) return null_buffer_text;
+        if (a->pack_bytes < lsr_view_pack_bytes(a->P, a->width, a->height, a->num_rendered))
+            return "pack_bytes is below lsr_view_pack_bytes";
+    }
     if (((reinterpret_cast<uintptr_t>(a->geom) | reinterpret_cast<uintptr_t>(a->image) |
           reinterpret_cast<uintptr_t>(a->binning) | reinterpret_cast<uintptr_t>(a->pack)) & 15) != 0 ||
         (reinterpret_cast<uintptr_t>(a->radii) & 3) != 0)
-        return bad("the buffers and the pack must be 16-byte aligned");
+        return "the buffers and the pack must be 16-byte aligned";
     if (a->reserved != 0 || (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD)))
-        return bad("unknown flag");
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
-    const bool debug = false;
+        return "unknown flag";
+    return nullptr;
+}
+
+// ViewParams of a view call; the caller sets R, overflow and plan_room, whose rules differ
+static ViewParams view_params(const lsr_view_args* a)
+{
     ViewParams v{};
     v.P = a->P;
     v.W = a->width;
     v.H = a->height;
     v.R_cap = a->capacity_rendered;
-    v.R = a->num_rendered;
     v.geom = static_cast<char*>(a->geom);
     v.image = static_cast<char*>(a->image);
     v.binning = static_cast<char*>(a->binning);
     v.pack = static_cast<char*>(a->pack);
     v.radii = a->radii;
+    v.fwd_flags = forward_flags_word(a->flags, a->fused_loss != 0);
+    return v;
+}
+
+static int32_t view_copy(const lsr_view_args* a, void* stream_ptr, bool restore)
+{
+    const char* who = restore ? "lsr_view_restore" : "lsr_view_save";
+    if (!a) return invalid(who, "null argument");
+    if (const char* why = view_args_error(a, false, "null buffer")) return invalid(who, why);
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    ViewParams v = view_params(a);
+    v.R = a->num_rendered;
     v.overflow = restore ? a->overflow : nullptr;
     v.plan_room = a->pack_bytes >= lsr_view_plan_pack_bytes(a->P, a->width, a->height, a->num_rendered);
-    // counters[kCntFwdFlags] as forward_impl publishes it
-    v.fwd_flags = ((a->flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) |
-                  (a->fused_loss ? kFwdFusedLoss : 0u) | ((a->flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) |
-                  ((a->flags & LSR_FWD_NO_BACKWARD) ? kFwdNoBackward : 0u);
     LSR_TRY(launch_view_copy(v, restore, stream), restore ? "view restore" : "view save");
     return LSR_OK;
 }
@@ -1216,50 +1264,17 @@ int32_t lsr_view_bind_layout(int32_t P, int32_t width, int32_t height, size_t* p
 
 int32_t lsr_view_bind(const lsr_view_args* a, int32_t bind_flags, void* stream_ptr)
 {
-    auto bad = [&](const char* what) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "lsr_view_bind: %s", what);
-        return fail(LSR_ERR_INVALID, msg);
-    };
-    if (!a) return bad("null argument");
-    if (bind_flags & ~LSR_BIND_CLAMPED) return bad("unknown bind flag");
-    if (a->P < 1 || a->width < 1 || a->height < 1 || a->width > 65535 * kTile || a->height > 65535 * kTile)
-        return bad("P, width and height must be positive");
-    if (a->capacity_rendered < 1 || a->capacity_entries < 1 || a->capacity_rendered > 0xFFFFFFFFll ||
-        a->capacity_entries > 0xFFFFFFFFll)
-        return bad("the capacities must be positive (both < 2^32)");
-    if (!a->geom || !a->image || !a->binning || !a->radii)
-        return bad("null buffer (the set's table and plane live in its geometry buffer)");
-    if (a->pack) {
-        if (a->num_rendered < 0 || a->num_rendered > a->capacity_rendered)
-            return bad("num_rendered must be 0 .. capacity_rendered");
-        if (a->pack_bytes < lsr_view_pack_bytes(a->P, a->width, a->height, a->num_rendered))
-            return bad("pack_bytes is below lsr_view_pack_bytes");
-    }
-    if (((reinterpret_cast<uintptr_t>(a->geom) | reinterpret_cast<uintptr_t>(a->image) |
-          reinterpret_cast<uintptr_t>(a->binning) | reinterpret_cast<uintptr_t>(a->pack)) & 15) != 0 ||
-        (reinterpret_cast<uintptr_t>(a->radii) & 3) != 0)
-        return bad("the buffers and the pack must be 16-byte aligned");
-    if (a->reserved != 0 || (a->flags & ~(LSR_FWD_ZERO_GRAD_RECORDS | LSR_FWD_NO_COLOR_GRAD | LSR_FWD_NO_BACKWARD)))
-        return bad("unknown flag");
+    static const char who[] = "lsr_view_bind";
+    if (!a) return invalid(who, "null argument");
+    if (bind_flags & ~LSR_BIND_CLAMPED) return invalid(who, "unknown bind flag");
+    if (const char* why = view_args_error(a, true, "null buffer (the set's table and plane live in its geometry buffer)"))
+        return invalid(who, why);
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
     const bool debug = false;
-    ViewParams v{};
-    v.P = a->P;
-    v.W = a->width;
-    v.H = a->height;
-    v.R_cap = a->capacity_rendered;
+    ViewParams v = view_params(a);
     v.R = a->pack ? a->num_rendered : 0;
-    v.geom = static_cast<char*>(a->geom);
-    v.image = static_cast<char*>(a->image);
-    v.binning = static_cast<char*>(a->binning);
-    v.pack = static_cast<char*>(a->pack);
-    v.radii = a->radii;
     v.overflow = a->pack ? a->overflow : nullptr;
     v.plan_room = a->pack && a->pack_bytes >= lsr_view_plan_pack_bytes(a->P, a->width, a->height, a->num_rendered);
-    v.fwd_flags = ((a->flags & LSR_FWD_ZERO_GRAD_RECORDS) ? kFwdZeroedRecords : 0u) |
-                  (a->fused_loss ? kFwdFusedLoss : 0u) | ((a->flags & LSR_FWD_NO_COLOR_GRAD) ? kFwdNoColorState : 0u) |
-                  ((a->flags & LSR_FWD_NO_BACKWARD) ? kFwdNoBackward : 0u);
     LSR_TRY(launch_view_bind(v, (bind_flags & LSR_BIND_CLAMPED) != 0, stream), "view bind");
     return LSR_OK;
 }
@@ -1500,11 +1515,7 @@ static const char* eval_shape_error(int32_t n_maps, int32_t H, int32_t W)
 int32_t lsr_eval_filter(const lsr_eval_filter_args* a, void* stream_ptr)
 {
     if (!a) return fail(LSR_ERR_INVALID, "lsr_eval_filter: null args");
-    if (const char* why = eval_shape_error(a->n_maps, a->H, a->W)) {
-        char buf[128];
-        snprintf(buf, sizeof(buf), "lsr_eval_filter: %s", why);
-        return fail(LSR_ERR_INVALID, buf);
-    }
+    if (const char* why = eval_shape_error(a->n_maps, a->H, a->W)) return invalid("lsr_eval_filter", why);
     if (!a->maps || !a->out_stats) return fail(LSR_ERR_INVALID, "lsr_eval_filter: null pointer");
     if ((reinterpret_cast<uintptr_t>(a->out_stats) & 7) != 0)
         return fail(LSR_ERR_INVALID, "lsr_eval_filter: out_stats must be 8-byte aligned");
@@ -1517,11 +1528,7 @@ int32_t lsr_eval_filter(const lsr_eval_filter_args* a, void* stream_ptr)
 int32_t lsr_eval_masks(const lsr_eval_mask_args* a, void* stream_ptr)
 {
     if (!a) return fail(LSR_ERR_INVALID, "lsr_eval_masks: null args");
-    if (const char* why = eval_shape_error(a->n_maps, a->H, a->W)) {
-        char buf[128];
-        snprintf(buf, sizeof(buf), "lsr_eval_masks: %s", why);
-        return fail(LSR_ERR_INVALID, buf);
-    }
+    if (const char* why = eval_shape_error(a->n_maps, a->H, a->W)) return invalid("lsr_eval_masks", why);
     if (!a->blend || !a->stats || !a->out_mask || (a->gt_mask && !a->out_counts))
         return fail(LSR_ERR_INVALID, "lsr_eval_masks: null pointer");
     if (a->gt_mask && (a->n_prompts < 1 || a->n_maps % a->n_prompts != 0))
@@ -1585,11 +1592,7 @@ size_t lsr_rgb_loss_scratch_bytes(int32_t planes, int32_t H, int32_t W)
 int32_t lsr_rgb_loss_forward(const lsr_rgb_loss_args* a, void* stream_ptr)
 {
     if (!a) return fail(LSR_ERR_INVALID, "lsr_rgb_loss_forward: null args");
-    if (const char* why = rgb_loss_shape_error(a->planes, a->H, a->W)) {
-        char buf[128];
-        snprintf(buf, sizeof(buf), "lsr_rgb_loss_forward: %s", why);
-        return fail(LSR_ERR_INVALID, buf);
-    }
+    if (const char* why = rgb_loss_shape_error(a->planes, a->H, a->W)) return invalid("lsr_rgb_loss_forward", why);
     if (!a->image || !a->target || !a->out_terms || !a->scratch)
         return fail(LSR_ERR_INVALID, "lsr_rgb_loss_forward: null pointer");
     if ((reinterpret_cast<uintptr_t>(a->scratch) & 7) != 0)
@@ -1603,11 +1606,7 @@ int32_t lsr_rgb_loss_forward(const lsr_rgb_loss_args* a, void* stream_ptr)
 int32_t lsr_rgb_loss_backward(const lsr_rgb_loss_bwd_args* a, void* stream_ptr)
 {
     if (!a) return fail(LSR_ERR_INVALID, "lsr_rgb_loss_backward: null args");
-    if (const char* why = rgb_loss_shape_error(a->planes, a->H, a->W)) {
-        char buf[128];
-        snprintf(buf, sizeof(buf), "lsr_rgb_loss_backward: %s", why);
-        return fail(LSR_ERR_INVALID, buf);
-    }
+    if (const char* why = rgb_loss_shape_error(a->planes, a->H, a->W)) return invalid("lsr_rgb_loss_backward", why);
     if (!a->image || !a->target || !a->maps || !a->dL_dloss || !a->out_dL_dimage)
         return fail(LSR_ERR_INVALID, "lsr_rgb_loss_backward: null pointer");
     hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
@@ -1705,7 +1704,21 @@ int32_t lsr_adam_multi(int32_t count, const lsr_adam_tensor* tensors, float grad
 }
 
 static int32_t adam_fill_language(const lsr_adam_tensor* t, float grad_scale, int64_t* step_dev, const int32_t* skip,
-                                  void* fill_record, int32_t raw, void* stream_ptr, int plane);
+                                  void* fill_record, int32_t raw, void* stream_ptr, int plane)
+{
+    if (!t || !step_dev || !fill_record || t->n < 0 || t->n % 3 != 0 || t->n / 3 > INT32_MAX ||
+        (t->n > 0 && (!t->param || !t->grad || !t->exp_avg || !t->exp_avg_sq)) ||
+        t->step < -((int64_t)1 << 40) || t->step > ((int64_t)1 << 40))
+        return fail(LSR_ERR_INVALID, "lsr_adam_fill_language: invalid argument");
+    if (reinterpret_cast<uintptr_t>(fill_record) & 15)
+        return fail(LSR_ERR_INVALID, "lsr_adam_fill_language: fill_record must be 16-byte aligned");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
+    const bool debug = false;
+    LSR_TRY(launch_adam_fill((int)(t->n / 3), t->grad, grad_scale, t->param, t->exp_avg, t->exp_avg_sq, adam_hyper(*t),
+                             step_dev, skip, reinterpret_cast<float4*>(fill_record), raw, stream, plane),
+            "adam fill");
+    return LSR_OK;
+}
 
 int32_t lsr_adam_fill_language(const lsr_adam_tensor* t, float grad_scale, int64_t* step_dev, const int32_t* skip,
                                void* fill_record, int32_t raw, void* stream)
@@ -1717,24 +1730,6 @@ int32_t lsr_adam_fill_language_plane(const lsr_adam_tensor* t, float grad_scale,
                                      void* fill_plane, int32_t raw, void* stream)
 {
     return adam_fill_language(t, grad_scale, step_dev, skip, fill_plane, raw, stream, 1);
-}
-
-static int32_t adam_fill_language(const lsr_adam_tensor* t, float grad_scale, int64_t* step_dev, const int32_t* skip,
-                                  void* fill_record, int32_t raw, void* stream_ptr, int plane)
-{
-    if (!t || !step_dev || !fill_record || t->n < 0 || t->n % 3 != 0 || t->n / 3 > INT32_MAX ||
-        (t->n > 0 && (!t->param || !t->grad || !t->exp_avg || !t->exp_avg_sq)) ||
-        t->step < -((int64_t)1 << 40) || t->step > ((int64_t)1 << 40))
-        return fail(LSR_ERR_INVALID, "lsr_adam_fill_language: invalid argument");
-    if (reinterpret_cast<uintptr_t>(fill_record) & 15)
-        return fail(LSR_ERR_INVALID, "lsr_adam_fill_language: fill_record must be 16-byte aligned");
-    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_ptr);
-    const bool debug = false;
-    const AdamHyper h{t->lr, t->beta1, t->beta2, t->eps, t->step};
-    LSR_TRY(launch_adam_fill((int)(t->n / 3), t->grad, grad_scale, t->param, t->exp_avg, t->exp_avg_sq, h, step_dev,
-                             skip, reinterpret_cast<float4*>(fill_record), raw, stream, plane),
-            "adam fill");
-    return LSR_OK;
 }
 
 int32_t lsr_language_tail(const lsr_settings* s, const lsr_backward_args* a, void* stream_ptr)
@@ -1755,11 +1750,10 @@ int32_t lsr_language_tail(const lsr_settings* s, const lsr_backward_args* a, voi
     const Layout L = make_layout(P, W, H, a->num_rendered, 0);
     float* grad = P > 0 ? reinterpret_cast<float*>(static_cast<char*>(a->geom_buffer) + L.grad_records) : nullptr;
     const lsr_adam_tensor& u = *a->update;
-    AdamHyper h{u.lr, u.beta1, u.beta2, u.eps, u.step};
     // the skip flag the all-reduce carried (the word after the language partials): any rank's overflow
     const int32_t* skip = P > 0 ? reinterpret_cast<const int32_t*>(grad + 3 * (size_t)P) : a->update_skip;
     LSR_TRY(launch_language_tail(P, a->radii, grad, const_cast<float*>(a->language_feature), u.exp_avg, u.exp_avg_sq,
-                                 a->dL_dmeans2D, a->dL_dlanguage_feature, h, a->update_step_dev, skip,
+                                 a->dL_dmeans2D, a->dL_dlanguage_feature, adam_hyper(u), a->update_step_dev, skip,
                                  reinterpret_cast<float4*>(a->fill_record), 1, stream,
                                  (a->flags & LSR_BIND_FILL_PLANE) ? 1 : 0),
             "language tail");
