@@ -505,9 +505,24 @@ int32_t lsr_densification_stats(int32_t P, const int32_t* radii, const float* dL
  * simple-knn's distCUDA2 (scene/gaussian_model.py:20,180): for each of the N points (N x 3 fp32),
  * the mean of the squared distances to its 3 nearest OTHER points (exact; a duplicate of a point
  * counts at distance 0; with N < 4 the missing neighbours count as FLT_MAX).  Scratch is requested
- * once through `alloc` (which = LSR_BUF_BACKWARD). */
+ * once through `alloc` (which = LSR_BUF_BACKWARD).
+ * Non-finite coordinates (inf, NaN) are the brute force's, unchanged: a point with one is nobody's
+ * neighbour (its squared distance to anything is inf or NaN, which is never smaller than a kept one)
+ * and its own output is (FLT_MAX + FLT_MAX + FLT_MAX) / 3 = inf; every other point's output is what
+ * the cloud without those points gives.  They are left out of the bounding box; no error is raised
+ * and the call does not wait for the device. */
 int32_t lsr_dist_cuda2(int64_t N, const float* points, float* out_mean_dist, lsr_alloc_fn alloc, void* alloc_user,
                        void* stream);
+
+/* Test hook, not part of the reference interface; host only, no device work.  The search grid
+ * lsr_dist_cuda2 would size for N points (1 .. 0x3FFFFFFF) with the bounding box
+ * box = {min x, y, z, max x, y, z}: out_origin_h = {x0, y0, z0, h, 1 / h}, out_dims = {nx, ny, nz}, by
+ * the function the device runs (langsplat_amd/csrc/lsr_knn.hip knn_grid_size).  For every bit
+ * pattern of box: 1 <= nx, ny, nz, nx * ny * nz <= 2 N + 64, h and 1 / h positive, finite and normal.
+ * An axis with min > max (no finite coordinate) has origin 0 and zero extent; a non-finite box value,
+ * or a cell size whose h or 1 / h is no normal float, gives one cell (1 x 1 x 1, h = 1).
+ * Added without a change of LSR_ABI_VERSION (purely additive): callers detect it by symbol. */
+int32_t lsr_debug_knn_grid(const float* box, int64_t N, float* out_origin_h, int32_t* out_dims);
 
 /* ---- open-vocabulary query ------------------------------------------
  * What eval/evaluate_iou_loc.py:258-266 does with a rendered language map, for N pixels in ONE

@@ -237,6 +237,8 @@ SIGNATURES = {
     "lsr_language_tail": (ctypes.c_int32, [ctypes.POINTER(LsrSettings), ctypes.POINTER(LsrBackwardArgs), _vp]),
     "lsr_densification_stats": (ctypes.c_int32, [ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lsr_dist_cuda2": (ctypes.c_int32, [ctypes.c_int64, _vp, _vp, ALLOC_FN, _vp, _vp]),
+    "lsr_debug_knn_grid": (ctypes.c_int32, [ctypes.POINTER(ctypes.c_float), ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)]),
     "lsr_masked_l1_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int64]),
     "lsr_masked_l1_forward": (ctypes.c_int32, [ctypes.c_int32, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int32, _vp, _vp,
                                                _vp]),
@@ -263,6 +265,8 @@ SIGNATURES = {
 OPTIONAL = ("lsr_view_bind_layout", "lsr_view_bind", "lsr_fill_language_plane", "lsr_adam_fill_language_plane")
 # the walk plan (include/lsr.h lsr_view_plan_pack_bytes), additive in the same way: has_view_plan()
 OPTIONAL_PLAN = ("lsr_view_plan_pack_bytes", "lsr_view_plan_layout")
+# test hooks added the same way (include/lsr.h lsr_debug_knn_grid)
+OPTIONAL_DEBUG = ("lsr_debug_knn_grid",)
 BIND_FORWARD, BIND_BACKWARD, BIND_FILL_PLANE, BIND_CLAMPED = 16, 16, 32, 1
 
 _lib: Optional[ctypes.CDLL] = None
@@ -278,7 +282,7 @@ def load(path: str = LIB_PATH) -> ctypes.CDLL:
         _build.build()
     lib = ctypes.CDLL(path)
     for name, (res, args) in SIGNATURES.items():
-        if name in OPTIONAL + OPTIONAL_PLAN and not hasattr(lib, name):
+        if name in OPTIONAL + OPTIONAL_PLAN + OPTIONAL_DEBUG and not hasattr(lib, name):
             continue
         fn = getattr(lib, name)
         fn.restype = res
@@ -1317,6 +1321,17 @@ def debug_render_stats():
     v = list(arr)
     return {"entries": v[0], "power_hit": v[1], "alpha_hit": v[2], "lanes_hit": v[3], "barrier_slots": v[4],
             "batches": v[6], "hist": v[8:8 + 65]}
+
+
+def debug_knn_grid(box, N):
+    """The search grid lsr_dist_cuda2 sizes for N points in the bounding box (min x, y, z, max x, y, z),
+    evaluated on the host (include/lsr.h lsr_debug_knn_grid): {"origin": (x0, y0, z0), "h", "inv_h",
+    "dims": (nx, ny, nz)}."""
+    b = (ctypes.c_float * 6)(*box)
+    o = (ctypes.c_float * 5)()
+    d = (ctypes.c_int32 * 3)()
+    _check(load().lsr_debug_knn_grid(b, N, o, d), "lsr_debug_knn_grid")
+    return {"origin": tuple(o[:3]), "h": o[3], "inv_h": o[4], "dims": tuple(d)}
 
 
 def debug_render_timeline(kernel, n):

@@ -1789,6 +1789,14 @@ int32_t lsr_dist_cuda2(int64_t N, const float* points, float* out_mean_dist, lsr
     return LSR_OK;
 }
 
+int32_t lsr_debug_knn_grid(const float* box, int64_t N, float* out_origin_h, int32_t* out_dims)
+{
+    if (!box || !out_origin_h || !out_dims || N < 1 || N > 0x3FFFFFFF)
+        return fail(LSR_ERR_INVALID, "lsr_debug_knn_grid: invalid argument");
+    knn_debug_grid(box, N, out_origin_h, out_dims);
+    return LSR_OK;
+}
+
 int32_t lsr_decode_language_feature(int32_t L, int32_t H, int32_t W, const int64_t* seg_map, int32_t level,
                                     int32_t N, int32_t D, const float* feature_map, float* out_feature,
                                     uint8_t* out_mask, void* stream_ptr)

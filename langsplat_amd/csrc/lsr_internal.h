@@ -486,6 +486,9 @@ hipError_t launch_publish_counters(int nb, const uint4* partial, uint32_t* count
 size_t knn_scratch_bytes(int64_t N);
 hipError_t launch_knn_mean_dist3(int64_t N, const float* pts, float* out, void* scratch, uint32_t* stall,
                                  hipStream_t s);
+// the grid the launch above would size for this bounding box, evaluated on the host (lsr_debug_knn_grid):
+// origin_h = {x0, y0, z0, h, inv_h}, dims = {nx, ny, nz}
+void knn_debug_grid(const float box[6], int64_t N, float origin_h[5], int32_t dims[3]);
 
 size_t masked_l1_scratch_bytes();
 hipError_t launch_masked_l1_forward(int C, int64_t HW, const float* pred, const float* gt, const void* mask,

@@ -3,8 +3,11 @@
 // Gaussian scales from the SfM point cloud).
 //
 // Exact 3-NN on a uniform grid, instead of simple-knn's Morton sort + box scan:
-//   1. bounding box (per-block partials, one-workgroup final reduction);
-//   2. grid of cubic cells sized for ~2 points per cell (at most 2N + 64 cells);
+//   1. bounding box of the finite coordinates, per axis (per-block partials, one-workgroup final
+//      reduction); an axis with no finite coordinate gets origin 0 and zero extent;
+//   2. grid of cubic cells sized for ~2 points per cell (at most 2N + 64 cells) by knn_grid_size,
+//      which ends after a fixed number of steps for every input and falls back to ONE cell (every
+//      thread then scans the whole cloud: exact, only slow) where no usable cell size exists;
 //   3. counting sort of the points by cell (cell counts, one scan, scatter);
 //   4. one thread per point, in cell order (neighbouring threads search neighbouring cells):
 //      shells of cells at Chebyshev distance r = 0, 1, 2, ... are scanned until the 3rd-best squared
@@ -14,6 +17,10 @@
 // d0 <= d1 <= d2 -- the operation order of oracle/lsr_oracle.c lso_knn_mean_dist3, so results are
 // bit-identical to the brute-force oracle.  The point itself is excluded by index (duplicates of it
 // count, at distance 0); with fewer than 4 points the missing neighbours are FLT_MAX, as upstream.
+// A point with a non-finite coordinate is nobody's neighbour (its squared distance is inf or NaN and
+// fails d < b2) and its own result is (FLT_MAX + FLT_MAX + FLT_MAX) / 3 = inf, as in the oracle: its
+// cell index is clamped (the float -> int convert saturates, NaN -> 0), its slack is inf or NaN, so its
+// search ends only when the cube covers the whole grid.
 #include <float.h>
 
 #include "lsr_internal.h"
@@ -21,6 +28,9 @@
 namespace lsr {
 
 constexpr int kKnnThreads = 256;
+
+// cells the scratch is sized for (knn_scratch_bytes) and the grid is held to (knn_grid_size)
+static inline int64_t knn_max_cells(int64_t N) { return 2 * (N > 0 ? N : 1) + 64; }
 
 struct KnnGrid {
     float x0, y0, z0, h, inv_h;
@@ -50,7 +60,17 @@ __device__ __forceinline__ void knn_insert(float d, float& b0, float& b1, float&
     }
 }
 
-// per-block min/max of the coordinates -> partial[6 * block]
+// a non-finite coordinate (inf, NaN) does not count for the bounding box
+__device__ __forceinline__ void knn_minmax(float p, float& lo, float& hi)
+{
+    if (fabsf(p) <= FLT_MAX) {
+        lo = fminf(lo, p);
+        hi = fmaxf(hi, p);
+    }
+}
+
+// per-block min/max of the finite coordinates -> partial[6 * block]; an axis the block saw no finite
+// coordinate of keeps {FLT_MAX, -FLT_MAX}
 __global__ __launch_bounds__(kKnnThreads) void k_knn_bbox_partial(int64_t N, const float* __restrict__ pts,
                                                                   float* __restrict__ partial)
 {
@@ -58,12 +78,9 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_bbox_partial(int64_t N, con
     float v[6] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (int64_t i = (int64_t)blockIdx.x * kKnnThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kKnnThreads) {
         const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-        v[0] = fminf(v[0], x);
-        v[1] = fminf(v[1], y);
-        v[2] = fminf(v[2], z);
-        v[3] = fmaxf(v[3], x);
-        v[4] = fmaxf(v[4], y);
-        v[5] = fmaxf(v[5], z);
+        knn_minmax(x, v[0], v[3]);
+        knn_minmax(y, v[1], v[4]);
+        knn_minmax(z, v[2], v[5]);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1)
@@ -83,7 +100,57 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_bbox_partial(int64_t N, con
     }
 }
 
-// one workgroup: final bounding box -> grid (cell size for ~2 points per cell, <= max_cells cells)
+constexpr int kKnnGridSteps = 256;  // cap of the sizing loop; a finite box needs fewer than 80 steps
+
+// Grid for the bounding box v = {min x, y, z, max x, y, z} of N points: cubic cells for ~2 points per
+// cell, at most max_cells of them.  Total: for every bit pattern of v it returns after at most
+// kKnnGridSteps steps with 1 <= nx, ny, nz, nx * ny * nz <= max_cells (max_cells >= 1) and h, inv_h
+// positive, finite and normal floats.  An axis with min > max (no finite coordinate seen: the
+// reductions start from {FLT_MAX, -FLT_MAX}) gets origin 0 and zero extent.  Where no such cell size
+// exists -- a non-finite box value (the reductions never produce one), h or 1 / h outside the normal
+// floats, or the cap reached -- the grid is ONE cell with h = 1, which the search scans whole.
+__host__ __device__ inline KnnGrid knn_grid_size(const float v[6], int64_t N, int64_t max_cells)
+{
+    KnnGrid g;
+    g.x0 = g.y0 = g.z0 = 0.0f;
+    g.h = g.inv_h = 1.0f;
+    g.nx = g.ny = g.nz = 1;
+    double e[3];
+    float o[3];
+    for (int k = 0; k < 3; k++) {
+        if (!(fabsf(v[k]) <= FLT_MAX) || !(fabsf(v[k + 3]) <= FLT_MAX)) return g;
+        const bool seen = v[k] <= v[k + 3];
+        o[k] = seen ? v[k] : 0.0f;
+        e[k] = seen ? (double)v[k + 3] - v[k] : 0.0;
+    }
+    g.x0 = o[0];
+    g.y0 = o[1];
+    g.z0 = o[2];
+    const double ex = e[0], ey = e[1], ez = e[2];
+    double ext = fmax(ex, fmax(ey, ez));
+    if (!(ext > 0.0)) ext = 1.0;  // all points coincide
+    // volume of the box with degenerate axes widened to 1% of the largest extent
+    const double fx = fmax(ex, 0.01 * ext), fy = fmax(ey, 0.01 * ext), fz = fmax(ez, 0.01 * ext);
+    double h = cbrt(fx * fy * fz / fmax(0.5 * (double)N, 1.0));
+    for (int step = 0; step < kKnnGridSteps; step++, h *= 1.26) {
+        const int nx = (int)fmin(ex / h + 1.0, 1048576.0);
+        const int ny = (int)fmin(ey / h + 1.0, 1048576.0);
+        const int nz = (int)fmin(ez / h + 1.0, 1048576.0);
+        if ((double)nx * ny * nz <= (double)max_cells) {
+            const float hf = (float)h, inv_hf = (float)(1.0 / h);
+            if (!(hf >= FLT_MIN && hf <= FLT_MAX && inv_hf >= FLT_MIN && inv_hf <= FLT_MAX)) return g;
+            g.h = hf;
+            g.inv_h = inv_hf;
+            g.nx = nx;
+            g.ny = ny;
+            g.nz = nz;
+            return g;
+        }
+    }
+    return g;
+}
+
+// one workgroup: final bounding box -> grid
 __global__ __launch_bounds__(64) void k_knn_grid(int nb, const float* __restrict__ partial, int64_t N, int64_t max_cells,
                                                  KnnGrid* __restrict__ grid)
 {
@@ -97,31 +164,7 @@ __global__ __launch_bounds__(64) void k_knn_grid(int nb, const float* __restrict
             const float w = __shfl_xor(v[k], o, 64);
             v[k] = k < 3 ? fminf(v[k], w) : fmaxf(v[k], w);
         }
-    if (threadIdx.x != 0) return;
-    const double ex = (double)v[3] - v[0], ey = (double)v[4] - v[1], ez = (double)v[5] - v[2];
-    double ext = fmax(ex, fmax(ey, ez));
-    if (!(ext > 0.0)) ext = 1.0;  // all points coincide (or N == 0)
-    // volume of the box with degenerate axes widened to 1% of the largest extent
-    const double fx = fmax(ex, 0.01 * ext), fy = fmax(ey, 0.01 * ext), fz = fmax(ez, 0.01 * ext);
-    double h = cbrt(fx * fy * fz / fmax(0.5 * (double)N, 1.0));
-    int nx, ny, nz;
-    for (;;) {
-        nx = (int)fmin(ex / h + 1.0, 1048576.0);
-        ny = (int)fmin(ey / h + 1.0, 1048576.0);
-        nz = (int)fmin(ez / h + 1.0, 1048576.0);
-        if ((double)nx * ny * nz <= (double)max_cells) break;
-        h *= 1.26;
-    }
-    KnnGrid g;
-    g.x0 = v[0];
-    g.y0 = v[1];
-    g.z0 = v[2];
-    g.h = (float)h;
-    g.inv_h = (float)(1.0 / h);
-    g.nx = nx;
-    g.ny = ny;
-    g.nz = nz;
-    *grid = g;
+    if (threadIdx.x == 0) *grid = knn_grid_size(v, N, max_cells);
 }
 
 __device__ __forceinline__ int knn_axis_cell(float p, float p0, float inv_h, int n)
@@ -211,10 +254,23 @@ __global__ __launch_bounds__(kKnnThreads) void k_knn_search(int64_t N, const Knn
     out[self] = (b0 + b1 + b2) / 3.0f;
 }
 
+void knn_debug_grid(const float box[6], int64_t N, float origin_h[5], int32_t dims[3])
+{
+    const KnnGrid g = knn_grid_size(box, N, knn_max_cells(N));
+    origin_h[0] = g.x0;
+    origin_h[1] = g.y0;
+    origin_h[2] = g.z0;
+    origin_h[3] = g.h;
+    origin_h[4] = g.inv_h;
+    dims[0] = g.nx;
+    dims[1] = g.ny;
+    dims[2] = g.nz;
+}
+
 size_t knn_scratch_bytes(int64_t N)
 {
     const size_t n = (size_t)(N > 0 ? N : 1);
-    const size_t cells = 2 * n + 64;
+    const size_t cells = (size_t)knn_max_cells((int64_t)n);
     const size_t nb = (n + kKnnThreads - 1) / kKnnThreads;
     const size_t pb = nb < 1024 ? nb : 1024;
     return align_up(sizeof(KnnGrid)) + align_up(4 * 6 * pb) + align_up(4 * n) + align_up(4 * (cells + 1)) +
@@ -226,7 +282,7 @@ hipError_t launch_knn_mean_dist3(int64_t N, const float* pts, float* out, void* 
 {
     if (N <= 0) return hipSuccess;
     const size_t n = (size_t)N;
-    const int64_t cells = 2 * (int64_t)n + 64;
+    const int64_t cells = knn_max_cells(N);
     const int nb = (int)((n + kKnnThreads - 1) / kKnnThreads);
     const int pb = nb < 1024 ? nb : 1024;
     char* p = static_cast<char*>(scratch);

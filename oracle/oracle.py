@@ -11,6 +11,7 @@ interface mirrors the reference call site gaussian_renderer/__init__.py:96-105.
 from __future__ import annotations
 
 import ctypes
+import fcntl
 import os
 import subprocess
 
@@ -47,10 +48,24 @@ FORM_KERNEL, FORM_UPSTREAM, FORM_UPSTREAM_FMA = 0, 1, 2
 
 
 def build(force: bool = False) -> str:
-    """Compile the oracle with its Makefile (gcc, -ffp-contract=off)."""
+    """Compile the oracle with its Makefile (gcc, -ffp-contract=off).
+
+    Several processes may get here at once (the gloo workers of tests/test_distributed.py each load
+    the oracle): one of them builds, under a lock on this directory, the others wait and find the
+    library fresh; the Makefile moves the finished library into place, so none loads a partial file."""
     src = os.path.join(_HERE, "lsr_oracle.c")
-    if force or not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src):
-        subprocess.run(["make", "-s", "-C", _HERE, "liblsr_oracle.so"], check=True)
+
+    def stale():
+        return not os.path.exists(_LIB_PATH) or os.path.getmtime(_LIB_PATH) < os.path.getmtime(src)
+
+    if force or stale():
+        fd = os.open(_HERE, os.O_RDONLY)
+        try:
+            fcntl.flock(fd, fcntl.LOCK_EX)
+            if force or stale():
+                subprocess.run(["make", "-s", "-C", _HERE, "liblsr_oracle.so"], check=True)
+        finally:
+            os.close(fd)
     return _LIB_PATH
 
 
